@@ -7,8 +7,15 @@ north-star size): one message per step carrying n = 2^28 dense float32 values
 (1 GiB, N(0,1), seed 1) and the chain [FIXING_FLOAT num_bytes=1] with min/max
 computed; a step encodes it on the worker's RemoteNode, delivers it and
 decodes it on the server's (libpsf psf_node_roundtrip: no Python per message).
-Payload = 4n bytes/step.  The same run also measures BASELINE configs[1]'s
-128M values (2^27) and reports it under "config_128M".
+Payload = 4n bytes/step.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the result line: nothing else.  `--dump-outputs DIR`
+also writes what the last timed step computed (see dump_outputs).  `--full`
+adds everything below to the same run: the per-kernel diagnostic pass and the
+live roofline, the host accounting, BASELINE configs[1]'s 128M values (2^27)
+under "config_128M", the companion C4 line under "config_c4", C1's wire line
+and the CPU baseline.
 
 N GPUs: rank g is server g of EvenDivide(N, g) and codes its own pre-placed
 shard (no data-path collective; weak scaling).  `python bench.py --gpus N`
@@ -17,20 +24,21 @@ unless WORLD_SIZE is already set (torchrun).  Timed region: barrier +
 synchronize, K steps, barrier + synchronize; the max elapsed over ranks is the
 job time.  value = N * K * payload / time.
 
-Other configs (--config): c1 (ctr push streams, batched), c3 / c3miss (10M
-keys @1% + values, KEY_CACHING hit / miss), c4 (64 push streams over 8 server
-key ranges, cross-range spill in one all-to-all-v per step), c5 (embedding
-rows dim 128 sliced over 8 servers, [KEY_CACHING, FIXING_FLOAT(, COMPRESSING)]).
+Other configs (--config), each a plain run unless --full is given: c1 (ctr
+push streams, batched), c3 / c3miss (10M keys @1% + values, KEY_CACHING hit /
+miss), c4 (64 push streams over 8 server key ranges, cross-range spill in one
+all-to-all-v per step), c5 (embedding rows dim 128 sliced over 8 servers,
+[KEY_CACHING, FIXING_FLOAT(, COMPRESSING)]).
 
-roofline: per-kernel durations from HIP events recorded on the launch stream
-around the dominant kernel inside the timed region (libpsf profiler); its
-algorithmic bytes / average duration vs 8 TB/s.  traffic: PMC-derived HBM bytes
-per launch from profiles/pmc_traffic.json when it matches this kernel and
-size (tools/pmc_traffic.py), else null.
-cpu_baseline: the C restatement of the reference's filter code (oracle/,
-"port") on the host cores of the same box, rank 0 at N=1 only, over a bounded
-sample of the same workload: one core where the reference's filters run
-serialised (C1-C3), one thread per stream / slice up to 16 for C4 / C5
+roofline (--full): per-kernel durations from HIP events recorded on the launch
+stream around the dominant kernel inside the timed region (libpsf profiler);
+its algorithmic bytes / average duration vs 8 TB/s.  traffic: PMC-derived HBM
+bytes per launch from profiles/pmc_traffic.json when it matches this kernel
+and size (tools/pmc_traffic.py), else null.
+cpu_baseline (--full): the C restatement of the reference's filter code
+(oracle/, "port") on the host cores of the same box, rank 0 at N=1 only, over
+a bounded sample of the same workload: one core where the reference's filters
+run serialised (C1-C3), one thread per stream / slice up to 16 for C4 / C5
 (SURVEY.md §8(d)).
 """
 from __future__ import annotations
@@ -49,6 +57,8 @@ sys.path.insert(0, ROOT)
 GIB = float(1 << 30)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, MI355X_MICROARCH.md
 CPU_THREADS_MAX = 16   # the GPU box's CPU share per GPU
+DUMP_MAX_ELEMS = 1 << 22  # --dump-outputs: elements kept of one array (16 MiB as float32)
+DUMP_SEED = 20240229      # --dump-outputs: seed of the sample's indices
 
 
 WORKLOADS = {
@@ -102,6 +112,14 @@ def parse(argv=None):
                     help="timed steps (default 20; 200 for c1 / c3, whose step is 0.04-0.07 ms: 20 of them "
                          "time only about 1 ms)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything else the line can report, in the same run: the per-kernel "
+                         "diagnostic pass and the live roofline, host accounting (and the c4 / c5 host floor), "
+                         "config_128M and config_c4 (c2), config_wire (c1) and the CPU baseline; the --no-* "
+                         "options below drop single parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; arrays "
+                         "over 2^22 elements as a fixed, seeded sample)")
     ap.add_argument("--n", type=int, default=1 << 28, help="c2: values per message (per GPU)")
     ap.add_argument("--nb", type=int, default=1, help="FIXING_FLOAT num_bytes")
     ap.add_argument("--bufs", type=int, default=3, help="distinct messages cycled through")
@@ -390,10 +408,15 @@ def build_workload(args, F, ctx, rank, world, dev, g, n):
                 lst.append(t)
         tmpls, snd, rcv = req + resp + push, wk + sv + wk, sv + wk + sv
 
-        def run(k, wire=False):
-            F.RemoteNode.roundtrip_many(snd, rcv, tmpls, k, phase_end=[S, 2 * S, 3 * S], wire=wire)
+        extra = {"key_bytes_elided": 16 * m * S, "wire": True}
+
+        def run(k, wire=False, keep=False):
+            last = F.RemoteNode.roundtrip_many(snd, rcv, tmpls, k, keep_last=keep, phase_end=[S, 2 * S, 3 * S],
+                                               wire=wire)
+            if keep:
+                extra["last"] = last
         # keys travel with the pull request only; the response and the push hit
-        return run, 32 * m * S, 2 * m * S, {"key_bytes_elided": 16 * m * S, "wire": True}
+        return run, 32 * m * S, 2 * m * S, extra
     if args.config == "c4pull":
         # the pull leg over C4's partition: requests out, per-range responses
         # answered from each rank's KVMap, merged back in key order
@@ -430,7 +453,7 @@ def build_workload(args, F, ctx, rank, world, dev, g, n):
             payload += 20 * keys.numel()  # request keys 8 B + response keys 8 B and value 4 B per key
         nloc = payload // 20
 
-        def run(k):
+        def run(k, keep=False):  # the router holds the last pull's arrays either way (pulled())
             router.pull(reqs, k)
         # keys travel with the first pull only; later requests and every response hit
         return run, payload, nloc, {"router": router, "key_bytes_elided": 16 * nloc, "store": kv}
@@ -472,7 +495,7 @@ def build_workload(args, F, ctx, rank, world, dev, g, n):
             payload += keys.numel() * (8 + 4 * dim)
             elided += 0 if args.miss else 8 * keys.numel()
 
-        def run(k):
+        def run(k, keep=False):  # the router holds the last step's messages either way (results())
             router.run(streams, k)
         return run, payload, nloc, {"router": router, "key_bytes_elided": elided}
     worker, server = F.RemoteNode(ctx), F.RemoteNode(ctx)
@@ -506,9 +529,81 @@ def build_workload(args, F, ctx, rank, world, dev, g, n):
             tmpls.append(t)
         payload = 12 * m
 
-    def run(k):
-        worker.roundtrip(server, tmpls, k)
-    return run, payload, n, {"key_bytes_elided": 8 * m if args.config == "c3" else 0}
+    extra = {"key_bytes_elided": 8 * m if args.config == "c3" else 0}
+
+    def run(k, keep=False):
+        last = worker.roundtrip(server, tmpls, k, keep_last=keep)
+        if keep:
+            extra["last"] = [last]
+    return run, payload, n, extra
+
+
+def dump_sample_index(n: int):
+    """The indices (a sorted int64 CPU tensor) --dump-outputs keeps of an array
+    of n elements, or None where it keeps them all."""
+    import torch
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    g = torch.Generator()
+    g.manual_seed(DUMP_SEED)
+    return torch.sort(torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=g))[0]
+
+
+def dump_outputs(args, extra, dev, rank, path):
+    """--dump-outputs: what the last timed step handed its caller, as
+    path/<name>.npy (rank 0; path/<name>_rank<r>.npy on the other ranks).
+
+    decoded_values (float32): the value arrays of the messages the step's
+    receivers decoded, concatenated in message order (c2 / c3: the one message;
+    c1: responses then pushes, by stream; c4 / c5: by (server, stream); c4pull:
+    the pulled arrays by stream).
+    encoded_codes (float32) and value_range (float64, one (min, max) row per
+    array): the FIXING_FLOAT codes the senders produced and the range each was
+    coded over; c1 / c2 / c3, whose driver returns the encoded messages.
+
+    An array of more than DUMP_MAX_ELEMS elements is written as its elements at
+    DUMP_MAX_ELEMS indices drawn (sorted, with replacement) from a generator
+    seeded with DUMP_SEED: the same indices for the same length."""
+    import numpy as np
+    import torch
+
+    from parameter_server_amd import filter as F
+    from parameter_server_amd import shard
+
+    def values(msgs):
+        out = []
+        for w in msgs:
+            for i in range(w.num_values()):
+                p, nbytes, loc = w.value_ptr(i)
+                out.append(F.copy_out(p, nbytes, loc, dev).to(dev))
+        return out
+
+    enc, ranges = None, None
+    router = extra.get("router")
+    if router is not None and args.config == "c4pull":
+        dec = values(w for _, w in sorted(router.pulled(), key=lambda sw: sw[0]))
+    elif router is not None:
+        dec = values(w for _, w in sorted(router.results(), key=lambda dw: (dw[0], shard.w_channel(dw[1]))))
+    else:
+        pairs = extra["last"]
+        dec = values(d for _, d in pairs)
+        enc = values(e for e, _ in pairs)
+        ff = 0 if args.config == "c2" else 1  # FIXING_FLOAT's place in the chain
+        ranges = [(fp[1], fp[3]) for e, _ in pairs if e.num_values() for fp in e.fixed_points(ff)]
+    torch.cuda.synchronize()
+    arrays = {"decoded_values": torch.cat([t.view(torch.float32) for t in dec]) if dec else None,
+              "encoded_codes": torch.cat(enc) if enc else None}
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        idx = dump_sample_index(t.numel())
+        if idx is not None:
+            t = t[idx.to(dev)]
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), t.to(torch.float32).cpu().numpy())
+    if ranges is not None:
+        np.save(os.path.join(path, f"value_range{suffix}.npy"), np.array(ranges, dtype=np.float64).reshape(-1, 2))
 
 
 def timed(run, steps, world, dist, ctx, prof_kernel=None, stride=1):
@@ -573,7 +668,7 @@ def main():
         if rank == 0:
             line = {"launch_check": True, "n_gpus": world_pg, "world_size": world_pg,
                     "backend": backend_pg, "config": {"workload": args.config}}
-            if args.config == "c2" and not args.no_c4:  # the companion line a real run adds (not measured here)
+            if args.full and args.config == "c2" and not args.no_c4:  # the companion line of a --full run
                 line["config_c4"] = c4_config(args, world_pg, backend_pg)
             print(json.dumps(line), flush=True)
         if world > 1:
@@ -593,10 +688,10 @@ def main():
     run(args.warmup)
     torch.cuda.synchronize()
 
-    # diagnostic pass (not timed): every kernel bracketed by HIP events, to
-    # find the dominant kernel and report the per-kernel breakdown
+    # diagnostic pass (--full; not timed): every kernel bracketed by HIP events,
+    # to find the dominant kernel and report the per-kernel breakdown
     diag = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         ctx.profile(True)
         ctx.profile_reset()
         run(min(args.steps, 10))
@@ -605,7 +700,7 @@ def main():
         ctx.profile(False)
     dom = max(diag, key=lambda k: diag[k][1]) if diag else None
 
-    # timed region: events only around the dominant kernel (live roofline),
+    # timed region; --full: events only around the dominant kernel (live roofline),
     # on every 4th launch of it (every 8th in the many-small-message configs):
     # a launch with start / stop events costs the stream a few us around the
     # kernel (stride 1 against 4, tools/ab_stride.sh r05o: C3 3272 -> 3324,
@@ -616,7 +711,11 @@ def main():
         router.exchange.bytes_sent = 0
     if router is not None:
         router.host_stats(reset=True)
-    elapsed, prof = timed(run, args.steps, world, dist, ctx, dom, stride)
+    keep = args.dump_outputs is not None and args.steps > 0
+    elapsed, prof = timed((lambda k: run(k, keep=True)) if keep else run, args.steps, world, dist, ctx, dom, stride)
+    if keep:
+        dump_outputs(args, extra, dev, rank, args.dump_outputs)
+        extra.pop("last", None)
     waits = ctx.host_waits()
     spill = router.exchange.bytes_sent if router is not None and router.exchange is not None else 0
     # host accounting of the timed steps (this rank): wall time, the part the
@@ -695,7 +794,7 @@ def main():
 
     # BASELINE configs[1] (128M values) measured in the same run
     also = None
-    if args.config == "c2" and not args.no_128m and n != (1 << 27):
+    if args.full and args.config == "c2" and not args.no_128m and n != (1 << 27):
         a2 = argparse.Namespace(**vars(args))
         a2.n = 1 << 27
         del run
@@ -713,7 +812,7 @@ def main():
     # assigner.h:17-28's partition); at N = 1 every slice is local
     c4 = None
     c4_failed = False
-    if args.config == "c2" and not args.no_c4:
+    if args.full and args.config == "c2" and not args.no_c4:
         if "run" in locals():
             del run
         try:
@@ -760,7 +859,7 @@ def main():
     # (its computed min/max settled to the host) and parsed by the receiver,
     # as Van::Send / Recv do after EncodeMessage (van.cc:122-191, 244-269)
     wire_line = None
-    if extra.get("wire"):
+    if args.full and extra.get("wire"):
         run(args.warmup, wire=True)
         elw, _ = timed(lambda k: run(k, wire=True), args.steps, world, dist, ctx)
         elw = max_over_ranks(elw)
@@ -769,7 +868,7 @@ def main():
                      "ms_per_step": round(elw / args.steps * 1e3, 4)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, nb)
 
     if rank == 0:

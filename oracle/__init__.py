@@ -48,15 +48,24 @@ KEY_CACHING, COMPRESSING, FIXING_FLOAT, NOISE = 1, 2, 3, 4
 PORT_OK, PORT_ERR_ARG, PORT_ERR_NBYTES, PORT_ERR_BIN = 0, -1, -2, -3
 
 
+def _protoc():
+    """The protoc that ships with torch (torch/bin/protoc), or None."""
+    import importlib.util
+    spec = importlib.util.find_spec("torch")
+    p = os.path.join(os.path.dirname(spec.origin), "bin", "protoc") if spec and spec.origin else ""
+    return p if os.access(p, os.X_OK) else None
+
+
 def build(ref: bool | None = None) -> None:
-    """Compile the C restatement (always), the reference's crc32c.cc (when
-    /root/reference is present) and the adapter harness (when libpsf is
-    built)."""
+    """Compile the C restatement (always), the reference's crc32c.cc and its
+    task.proto's descriptor set (when the reference's sources are present) and
+    the adapter harness (when libpsf is built)."""
     subprocess.check_call(["make", "-s", "-C", HERE, "port"])
     if ref is None:
         ref = os.path.isfile("/root/reference/src/util/crc32c.cc")
     if ref:
-        subprocess.check_call(["make", "-s", "-C", HERE, "ref"])
+        protoc = _protoc()
+        subprocess.check_call(["make", "-s", "-C", HERE, "ref"] + ([f"PROTOC={protoc}"] if protoc else []))
     if os.path.exists(os.path.join(os.path.dirname(HERE), "parameter_server_amd", "libpsf.so")):
         subprocess.check_call(["make", "-s", "-C", HERE, "adapter"])
 

@@ -22,6 +22,10 @@ from the restatements, cross-checked where the real thing exists here:
                                  ctr chain, FIXING_FLOAT message rules,
                                  COMPRESSING) of oracle/chain.py
   even_divide.json               Range<Key>::EvenDivide (oracle/slicing.py)
+  wire_frames.npz                malformed and nested Task frames with the
+                                 verdict of protobuf's runtime under the
+                                 reference's schema (oracle/_ref/ps_task.desc;
+                                 the frames come from tests/test_wire.py)
 The committed files were first written in round 1 by a harness that compiled
 the reference's filter headers against hand-written stand-ins for the types
 they need; that harness pins nothing and is gone, and --check shows the
@@ -102,8 +106,8 @@ def gen_ff(P):
     return {"ff_cases.npz": arrays, "ff_cases.json": meta}
 
 
-def gen_crc(P):
-    R = oracle.RefCrc32c()  # the reference's crc32c.cc
+def gen_crc(P, ref=True):
+    R = oracle.RefCrc32c() if ref else P  # the reference's crc32c.cc; without it the port alone
     rng = np.random.default_rng(7)
     lens = [0, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 100, 255, 256, 1000,
             2047, 2048, 2049, 4096, 10000, 65537]
@@ -233,11 +237,27 @@ def gen_scenarios(P):
     }}
 
 
-def generate(snappy=True):
+def gen_wire():
+    """Task frames + protobuf's verdict (tests/test_wire.py's generators) under
+    the reference's schema; {} where the build did not compile it."""
+    import test_wire
+    ref = test_wire._reference_types()
+    if ref is None:
+        return {}
+    arrays = {}
+    for kind, gen in (("malformed", test_wire.malformed_frames), ("nested", test_wire.nested_frames)):
+        frames = gen(ref[0])
+        arrays[f"{kind}_data"] = np.frombuffer(b"".join(b for b, _ in frames), np.uint8)
+        arrays[f"{kind}_offsets"] = np.cumsum([0] + [len(b) for b, _ in frames]).astype(np.int64)
+        arrays[f"{kind}_ok"] = np.array([ok for _, ok in frames], np.uint8)
+    return {"wire_frames.npz": arrays}
+
+
+def generate(snappy=True, ref=True):
     P = oracle.Port()
     out = {}
     out.update(gen_ff(P))
-    out.update(gen_crc(P))
+    out.update(gen_crc(P, ref))
     out.update(gen_noise(P))
     if snappy:
         S = oracle.Snappy118()
@@ -245,6 +265,7 @@ def generate(snappy=True):
         out.update(gen_snappy_malformed(P, S))
     out.update(gen_scenarios(P))
     out.update(gen_even_divide())
+    out.update(gen_wire())
     return out
 
 
@@ -258,9 +279,10 @@ def _same(name, data):
         for k in data)
 
 
-def check(snappy=True):
-    """names of the committed fixtures the generators do NOT reproduce"""
-    return [name for name, data in generate(snappy).items() if not _same(name, data)]
+def check(snappy=True, ref=True):
+    """names of the committed fixtures the generators do NOT reproduce; ref:
+    oracle/_ref is built (else CRC32C comes from the port alone)"""
+    return [name for name, data in generate(snappy, ref).items() if not _same(name, data)]
 
 
 def main():

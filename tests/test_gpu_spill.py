@@ -288,7 +288,7 @@ def test_push_router_world2_same_gpu(native):
 
 @pytest.mark.parametrize("gpus", [1, 2])
 def test_bench_default_reports_c4_spill(gpus):
-    """bench.py's default command (c2) with its companion C4 line, small sizes:
+    """bench.py's default command (c2) with --full's companion C4 line, small sizes:
     at --gpus 2 (two ranks sharing cuda:0 over gloo, the rehearsal knobs) the
     C4 slices for the other rank's servers travel in the all-to-all-v and
     config_c4 reports the spilled bytes; at --gpus 1 nothing spills."""
@@ -299,8 +299,8 @@ def test_bench_default_reports_c4_spill(gpus):
     env = dict(os.environ, PSF_DIST_BACKEND="gloo", PSF_SAME_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--n", str(1 << 20),
-                          "--c4-m", str(1 << 14), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--full",
+                          "--n", str(1 << 20), "--c4-m", str(1 << 14), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
                           "--no-profile", "--no-128m"], env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(x) for x in out.stdout.splitlines() if x.startswith("{")]

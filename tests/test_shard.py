@@ -253,8 +253,8 @@ def test_bench_launcher_gloo_world2():
 
 
 def test_bench_launcher_default_carries_config_c4():
-    """The default (c2) multi-GPU command also runs C4's cross-range spill and
-    reports it as config_c4 (its world size, backend, strong scaling)."""
+    """The default (c2) multi-GPU command with --full also runs C4's cross-range
+    spill and reports it as config_c4 (its world size, backend, strong scaling)."""
     import json
     import subprocess
     import sys
@@ -262,8 +262,8 @@ def test_bench_launcher_default_carries_config_c4():
     env = dict(os.environ, PSF_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--launch-check"],
-                         env=env, capture_output=True, text=True, timeout=180)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full",
+                          "--launch-check"], env=env, capture_output=True, text=True, timeout=180)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [json.loads(x) for x in out.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1, out.stdout

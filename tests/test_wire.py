@@ -2,9 +2,10 @@
 
 The reference serialises Task with protobuf-generated C++.  The message types
 come from the reference's own .proto files (system/proto/task.proto and its
-imports: filter.proto, range.proto, param.proto, ...), compiled here by the
-image's protoc (torch/bin/protoc) into a descriptor set and loaded into
-protobuf's Python runtime.  Where /root/reference is absent the tests fall
+imports: filter.proto, range.proto, param.proto, ...), compiled by the build
+(oracle.build(): `make -C oracle ref` with torch/bin/protoc) into the
+descriptor set oracle/_ref/ps_task.desc and loaded into protobuf's Python
+runtime.  Where the build had no reference to compile the tests fall
 back to descriptors typed from the same field numbers and types, and
 test_fallback_descriptors_match_reference_proto pins that fallback to the
 compiled ones.  Checks:
@@ -13,39 +14,32 @@ compiled ones.  Checks:
 * protobuf frames (any field order, packed repeats, unknown fields) parse to
   the same fields in libpsf;
 * truncated / corrupted frames are rejected exactly where protobuf's C++
-  ParseFromArray (parse + required fields) rejects them.
+  ParseFromArray (parse + required fields) rejects them.  The frames and
+  protobuf's verdicts under the reference's schema are recorded in
+  tests/golden/wire_frames.npz (the fallback lacks the fields outside the
+  filter path, which libpsf checks too), and generated again where the build
+  compiled that schema.
 """
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 pb = pytest.importorskip("google.protobuf")
 
-REF_SRC = "/root/reference/src"
-
-
-def _protoc():
-    import torch
-    p = os.path.join(os.path.dirname(torch.__file__), "bin", "protoc")
-    return p if os.access(p, os.X_OK) else None
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF_DESC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref",
+                        "ps_task.desc")
 
 
 def _reference_types():
-    """PS.Task / PS.FilterConfig compiled from the reference's task.proto (and
-    everything it imports), or None where the reference or protoc is absent."""
-    protoc = _protoc()
-    if protoc is None or not os.path.exists(os.path.join(REF_SRC, "system/proto/task.proto")):
+    """PS.Task / PS.FilterConfig from the reference's task.proto (and everything
+    it imports) as the build compiled them, or None where it could not."""
+    if not os.path.exists(REF_DESC):
         return None
     from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "ps.desc")
-        subprocess.run([protoc, f"-I{REF_SRC}", "--include_imports", f"--descriptor_set_out={out}",
-                        "system/proto/task.proto"], check=True, capture_output=True)
-        with open(out, "rb") as f:
-            fds = descriptor_pb2.FileDescriptorSet.FromString(f.read())
+    with open(REF_DESC, "rb") as f:
+        fds = descriptor_pb2.FileDescriptorSet.FromString(f.read())
     pool = descriptor_pool.DescriptorPool()
     for fd in fds.file:  # dependencies first (--include_imports order)
         pool.Add(fd)
@@ -143,7 +137,7 @@ def _fields(desc, seen=None):
 def test_fallback_descriptors_match_reference_proto():
     ref = _reference_types()
     if ref is None:
-        pytest.skip("reference .proto files or protoc absent")
+        pytest.skip("oracle/_ref/ps_task.desc not built (the build had no reference .proto files or protoc)")
     want, got = _fields(ref[0].DESCRIPTOR), _fields(_fallback_types()[0].DESCRIPTOR)
     assert set(got) <= set(want)
     for msg, fields in got.items():
@@ -340,13 +334,30 @@ def test_parse_packed_and_reordered(Task):
     assert Task.FromString(m.task_bytes()) == _filter_path_view(Task, want)
 
 
-def test_malformed_frames_rejected_like_protobuf(Task):
+def _pb_accepts(Task, b: bytes) -> bool:
+    """C++ ParseFromArray == parse + IsInitialized (required fields)"""
     from google.protobuf.message import DecodeError
+    try:
+        return Task.FromString(b).IsInitialized()
+    except DecodeError:
+        return False
 
+
+def _psf_accepts(b: bytes) -> bool:
     from parameter_server_amd import filter as F
     from parameter_server_amd._lib import PsfError
+    try:
+        F.Message.from_task_bytes(b)
+        return True
+    except PsfError:
+        return False
+
+
+def malformed_frames(Task):
+    """[(frame, protobuf's verdict)]: 4000 random Tasks of the reference's
+    schema, serialised, then cut, with one byte changed or one inserted."""
     rng = np.random.default_rng(2)
-    agree = rejected = 0
+    out = []
     for i in range(4000):
         b = bytearray(_random_pb(Task, rng).SerializeToString())
         op = i % 3
@@ -356,17 +367,51 @@ def test_malformed_frames_rejected_like_protobuf(Task):
             b[int(rng.integers(0, len(b)))] = int(rng.integers(0, 256))
         else:
             b.insert(int(rng.integers(0, len(b) + 1)), int(rng.integers(0, 256)))
-        try:  # C++ ParseFromArray == parse + IsInitialized (required fields)
-            ok_pb = Task.FromString(bytes(b)).IsInitialized()
-        except DecodeError:
-            ok_pb = False
-        try:
-            F.Message.from_task_bytes(bytes(b))
-            ok = True
-        except PsfError:
-            ok = False
-        assert ok == ok_pb, bytes(b)
-        agree += 1
+        out.append((bytes(b), _pb_accepts(Task, bytes(b))))
+    return out
+
+
+def nested_frames(Task):
+    """[(frame, protobuf's verdict)]: fields libpsf skips, malformed and well
+    formed in turn (see test_nested_fields_outside_filter_path_checked_like_protobuf)."""
+    cases = []
+    t = Task()
+    t.ctrl.SetInParent()
+    cases.append(t.SerializePartialToString())
+    t.ctrl.cmd = 2
+    cases.append(t.SerializePartialToString())
+    t = Task()
+    t.task.add().key_range.begin = 5
+    cases.append(t.SerializePartialToString())
+    t.task[0].key_range.end = 9
+    cases.append(t.SerializePartialToString())
+    cases.append(bytes([0x92, 0x01, 2, 8, 7]))  # ctrl { cmd: 7 } -- not a Control.Command
+    cases.append(bytes([0x92, 0x01, 2, 8, 4]))  # ctrl { cmd: READY_TO_EXIT }
+    cases.append(bytes([6 << 3 | 2, 2, 1, 0x81]))  # packed wait_time cut inside a varint
+    cases.append(bytes([6 << 3 | 2, 2, 1, 0x01]))
+    return [(b, _pb_accepts(Task, b)) for b in cases]
+
+
+def _recorded(kind, generate):
+    """The frames and protobuf verdicts of `generate` under the reference's
+    schema as tests/golden/wire_frames.npz records them (make_golden.py); where
+    the build compiled that schema they are generated again and must agree."""
+    a = np.load(os.path.join(GOLDEN, "wire_frames.npz"), allow_pickle=False)
+    d, off, ok = a[f"{kind}_data"], a[f"{kind}_offsets"], a[f"{kind}_ok"]
+    frames = [(d[off[i]:off[i + 1]].tobytes(), bool(ok[i])) for i in range(len(ok))]
+    ref = _reference_types()
+    if ref is not None:
+        assert generate(ref[0]) == frames
+    return frames
+
+
+def test_malformed_frames_rejected_like_protobuf():
+    frames = _recorded("malformed", malformed_frames)
+    assert len(frames) == 4000
+    rejected = 0
+    for b, ok_pb in frames:
+        ok = _psf_accepts(b)
+        assert ok == ok_pb, b
         rejected += not ok
     assert rejected > 100
 
@@ -391,44 +436,14 @@ def test_frames_follow_van_send(Task):
     assert len(fr) == 2 and not Task.FromString(fr[0]).HasField("has_key")
 
 
-def test_nested_fields_outside_filter_path_checked_like_protobuf(Task):
+def test_nested_fields_outside_filter_path_checked_like_protobuf():
     """Fields libpsf skips are still parsed as protobuf parses them: a nested
     Control without its required cmd, a nested Task whose key_range lacks end,
     an unknown enum value in a required field, a packed repeat cut inside a
     varint -- all rejected, and their well-formed twins accepted."""
-    from google.protobuf.message import DecodeError
-
-    from parameter_server_amd import filter as F
-    from parameter_server_amd._lib import PsfError
-    fields = Task.DESCRIPTOR.fields_by_name
-    if "ctrl" not in fields:
-        pytest.skip("reference .proto files absent: the fallback Task has no ctrl / task fields")
-    cases = []
-    t = Task()
-    t.ctrl.SetInParent()
-    cases.append(t.SerializePartialToString())
-    t.ctrl.cmd = 2
-    cases.append(t.SerializePartialToString())
-    t = Task()
-    t.task.add().key_range.begin = 5
-    cases.append(t.SerializePartialToString())
-    t.task[0].key_range.end = 9
-    cases.append(t.SerializePartialToString())
-    cases.append(bytes([0x92, 0x01, 2, 8, 7]))  # ctrl { cmd: 7 } -- not a Control.Command
-    cases.append(bytes([0x92, 0x01, 2, 8, 4]))  # ctrl { cmd: READY_TO_EXIT }
-    cases.append(bytes([6 << 3 | 2, 2, 1, 0x81]))  # packed wait_time cut inside a varint
-    cases.append(bytes([6 << 3 | 2, 2, 1, 0x01]))
     verdicts = []
-    for b in cases:
-        try:
-            ok_pb = Task.FromString(b).IsInitialized()
-        except DecodeError:
-            ok_pb = False
-        try:
-            F.Message.from_task_bytes(b)
-            ok = True
-        except PsfError:
-            ok = False
+    for b, ok_pb in _recorded("nested", nested_frames):
+        ok = _psf_accepts(b)
         assert ok == ok_pb, b
         verdicts.append(ok)
     assert verdicts == [False, True] * 4

@@ -36,7 +36,7 @@ for r in $(seq 1 $ROUNDS); do
       for c in $CONFIGS; do
         args="--config $c"
         case $c in c5z) args="--config c5 --compress";; c5zm) args="--config c5 --compress --miss";; esac
-        out=$(env $e PSF_LIBRARY_VARIANT=$L timeout -k 10 300 python bench.py $args --no-cpu-baseline $EXTRA 2>$O/err.log | tail -1) \
+        out=$(env $e PSF_LIBRARY_VARIANT=$L timeout -k 10 300 python bench.py $args --full --no-cpu-baseline $EXTRA 2>$O/err.log | tail -1) \
           || { echo "bench failed: $v $e $c"; tail -20 $O/err.log; exit 1; }
         echo "{\"variant\": \"$v\", \"env\": \"$e\", \"config\": \"$c\", \"round\": $r, \"line\": $out}" >> $O/runs.jsonl
         echo "$r $v [$e] $c $(echo "$out" | grep -o '"value": [0-9.]*' | head -1)"

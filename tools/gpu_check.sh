@@ -23,8 +23,8 @@ for s in "$@"; do
     pytestall) step pytest_gpu 900 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread ;;
     hostedge) step host_edge 300 python tools/host_edge.py ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py ;;
-    benchq) step bench 600 python bench.py --no-cpu-baseline --steps 20 ;;
+    bench) step bench 600 python bench.py --full ;;
+    benchq) step bench 600 python bench.py --full --no-cpu-baseline --steps 20 ;;
     prof) step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- python3 bench.py --no-cpu-baseline --steps 20 ;;
     *) echo "unknown step $s" ;;
   esac

@@ -12,7 +12,7 @@ p=29511
 for c in c2 c4 c5; do
   extra=""; [ $c = c5 ] && extra="--compress"
   PSF_SAME_GPU=1 PSF_DIST_BACKEND=gloo timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port $p bench.py --gpus 2 --config $c $extra --steps 5 --warmup 2 --no-cpu-baseline \
+    --master-addr 127.0.0.1 --master-port $p bench.py --gpus 2 --config $c $extra --full --steps 5 --warmup 2 --no-cpu-baseline \
     > $O/n2_$c.json 2> $O/n2_$c.err || exit 1
   p=$((p + 1))
 done
