@@ -149,7 +149,7 @@ int port_ff_decode(const uint8_t* code, size_t code_bytes, int dtype, int nb,
   return PORT_OK;
 }
 
-/* Checker for the device decode's quotient (ff_codec.hip dequant_q): counts
+/* Checker for the device decode's quotient (ff_kernels.h dequant_q): counts
  * the codes r in [0, 2^(8nb)) where the fma-corrected reciprocal product
  * q0 = r * RN(1/ratio); q = fma(fma(-q0, ratio, r), RN(1/ratio), q0)
  * differs from the IEEE quotient r / ratio the reference computes

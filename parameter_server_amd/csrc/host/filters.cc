@@ -1,6 +1,6 @@
 // Codec filters of libpsf (host side).  Each method cites the reference lines
 // whose behaviour it keeps; the element work runs in the HIP kernels of
-// ff_codec.hip / crc32c.hip / snappy.hip / noise.hip.
+// ff_kernels.h (launched by ff_codec.hip) / crc32c.hip / snappy.hip / noise.hip.
 #include <math.h>
 
 #include <algorithm>
@@ -134,7 +134,7 @@ void FixingFloatFilter::convert(Message* msg, bool encode) {  // fixing_float.h:
 }
 
 namespace {
-struct FfJob {
+struct FfWork {
   Message* msg;
   int i;     // value index
   int type;  // FLOAT / DOUBLE
@@ -144,6 +144,13 @@ struct FfJob {
   size_t elems;
   const float* range = nullptr;  // decode: the encode's device {min, max}
   bool stored = false;           // encode: codes into a stored snappy stream (COMPRESSING next)
+  size_t out_bytes = 0;          // to allocate for `out`
+  // encode, per chunk of publish slots:
+  int slot = 0;         // index in the chunk: its publish slot
+  uint32_t ticket = 0;  // of the publish slot; 0: none (preset range, or lazy)
+  int lazy_idx = -1;    // record in the chunk's RangeBatch, or -1
+  FixedPoint preset{};
+  uint32_t seed = 0;
 };
 
 // Whether msg's COMPRESSING encode comes right after its FIXING_FLOAT encode
@@ -165,7 +172,7 @@ bool compressing_follows(const Message* msg) {
 
 // the value arrays FixingFloatFilter::convert touches in one message
 // (fixing_float.h:24-47); false when num_bytes == 0 (the filter does nothing)
-bool collect_jobs(Message* msg, std::vector<FfJob>* jobs) {
+bool collect_jobs(Message* msg, std::vector<FfWork>* jobs) {
   FilterConfig* conf = Filter::find(FilterConfig::FIXING_FLOAT, msg);
   if (!conf) throw CheckError(kErrCheck, "CHECK_NOTNULL(find(FIXING_FLOAT))");
   if (conf->num_bytes == 0) return false;
@@ -179,7 +186,7 @@ bool collect_jobs(Message* msg, std::vector<FfJob>* jobs) {
     const int type = msg->task.value_type[i];
     if ((int)conf->fixed_point.size() <= k) conf->fixed_point.emplace_back();
     if (type == kFloat || type == kDouble)
-      jobs->push_back(FfJob{msg, i, type, conf->num_bytes, &conf->fixed_point[k++], {}, {}, 0, nullptr});
+      jobs->push_back(FfWork{msg, i, type, conf->num_bytes, &conf->fixed_point[k++], {}, {}, 0, nullptr});
   }
   if (jobs->size() > first) {
     const int nb = conf->num_bytes;
@@ -188,41 +195,41 @@ bool collect_jobs(Message* msg, std::vector<FfJob>* jobs) {
   return true;
 }
 
-// Outputs of jobs [b, e): one HBM block carved into 256-byte aligned
-// sub-buffers that share its owner when there are several (one allocator call
-// per batch instead of one per message), a plain buffer for one.
-void alloc_outputs(Context* ctx, std::vector<FfJob>& jobs, size_t b, size_t e,
-                   const std::vector<size_t>& bytes) {
-  if (e - b == 1) {
-    jobs[b].out = ctx->alloc(bytes[0]);
+// Outputs (out_bytes each) of the jobs listed in `idx`: one HBM block carved,
+// in that order, into 256-byte aligned sub-buffers that share its owner when
+// there are several (one allocator call per batch instead of one per
+// message), a plain buffer for one.
+void alloc_outputs(Context* ctx, std::vector<FfWork>& jobs, const std::vector<size_t>& idx) {
+  if (idx.size() == 1) {
+    jobs[idx[0]].out = ctx->alloc(jobs[idx[0]].out_bytes);
     return;
   }
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t total = 0;
-  for (size_t q = b; q < e; ++q) total += up(bytes[q - b]);
+  for (size_t q : idx) total += up(jobs[q].out_bytes);
   Buffer blk = ctx->alloc(total);
   size_t off = 0;
-  for (size_t q = b; q < e; ++q) {
+  for (size_t q : idx) {
     Buffer& o = jobs[q].out;
     o.owner = blk.owner;
     o.ptr = blk.ptr + off;
-    o.bytes = bytes[q - b];
+    o.bytes = jobs[q].out_bytes;
     o.loc = Loc::kDevice;
-    off += up(bytes[q - b]);
+    off += up(jobs[q].out_bytes);
   }
 }
 
 // jobs [b, e) grouped for batched launches: same (type, nb), batchable
 // (groups in a flat list: a batch almost always has one)
 template <typename F, typename G>
-void for_each_batch(std::vector<FfJob>& jobs, size_t b, size_t e, bool encode, F&& launch_one, G&& launch_batch) {
+void for_each_batch(std::vector<FfWork>& jobs, size_t b, size_t e, bool encode, F&& launch_one, G&& launch_batch) {
   struct Group {
     int type, nb;
     std::vector<size_t> q;
   };
   std::vector<Group> groups;
   for (size_t q = b; q < e; ++q) {
-    FfJob& j = jobs[q];
+    FfWork& j = jobs[q];
     // a stored-layout output is written by the batched kernel only, even alone
     if ((e - b > 1 || j.stored) && ff_batchable(j.in.ptr, j.out.ptr, j.elems, j.nb, j.type, encode)) {
       Group* g = nullptr;
@@ -263,7 +270,7 @@ void for_each_batch(std::vector<FfJob>& jobs, size_t b, size_t e, bool encode, F
 // batched launches of up to kFfBatchMax arrays (one launch per kernel for a
 // whole batch of small messages).
 void FixingFloatFilter::encode_messages(Context* ctx, std::vector<FfMessage>& msgs, bool lazy) {
-  std::vector<FfJob> jobs;
+  std::vector<FfWork> jobs;
   jobs.reserve(msgs.size());
   for (auto& m : msgs) collect_jobs(m.msg, &jobs);
   if (jobs.empty()) return;
@@ -273,41 +280,39 @@ void FixingFloatFilter::encode_messages(Context* ctx, std::vector<FfMessage>& ms
   const size_t chunk = lazy ? std::max<size_t>(jobs.size(), 1) : (size_t)Context::kSyncSlots;
   for (size_t base = 0; base < jobs.size(); base += chunk) {
     const size_t end = std::min(jobs.size(), base + chunk);
-    std::vector<uint32_t> tickets(end - base, 0);
-    std::vector<FixedPoint> presets(end - base);
-    std::vector<uint32_t> seeds(end - base);
-    std::vector<int> lazy_idx(end - base, -1);
-    std::vector<size_t> out_bytes(end - base);
+    std::vector<size_t> chunk_idx;
+    chunk_idx.reserve(end - base);
     int nlazy = 0;
     for (size_t q = base; q < end; ++q) {
-      FfJob& j = jobs[q];
+      FfWork& j = jobs[q];
+      chunk_idx.push_back(q);
+      j.slot = (int)(q - base);
       j.fp->settle();  // a config still pending from an earlier encode
       const size_t vsz = j.type == kFloat ? 4 : 8;
       j.in = ctx->to_device(j.msg->value[j.i]);
       j.elems = j.in.bytes / vsz;
       if (j.elems == 0) throw CheckError(kErrArg, "value array shorter than one element");
-      FixedPoint& preset = presets[q - base];
-      preset = FixedPoint{j.fp->has_min, j.fp->has_max, j.fp->min_value, j.fp->max_value};
-      if (preset.has_min && preset.has_max) {
-        if (!((double)preset.max_value - (double)preset.min_value > 0))
+      j.preset = FixedPoint{j.fp->has_min, j.fp->has_max, j.fp->min_value, j.fp->max_value};
+      if (j.preset.has_min && j.preset.has_max) {
+        if (!((double)j.preset.max_value - (double)j.preset.min_value > 0))
           throw CheckError(kErrBin, "CHECK_GT(bin, 0)");
       } else if (lazy) {
-        lazy_idx[q - base] = nlazy++;
+        j.lazy_idx = nlazy++;
       } else {
-        tickets[q - base] = ctx->next_ticket();
+        j.ticket = ctx->next_ticket();
       }
-      out_bytes[q - base] = j.elems * (size_t)j.nb;
-      j.stored = ctx->device() >= 0 && (j.nb == 1 || j.nb == 2) && out_bytes[q - base] < (1ull << 32) &&
-                 j.in.loc == Loc::kDevice && (reinterpret_cast<uintptr_t>(j.in.ptr) % (j.type == kFloat ? 4 : 8)) == 0 &&
+      j.out_bytes = j.elems * (size_t)j.nb;
+      j.stored = ctx->device() >= 0 && (j.nb == 1 || j.nb == 2) && j.out_bytes < (1ull << 32) &&
+                 j.in.loc == Loc::kDevice && (reinterpret_cast<uintptr_t>(j.in.ptr) % vsz) == 0 &&
                  compressing_follows(j.msg);
       // the whole stored stream (64 bytes to spare for the compressor's
       // aligned reads past a fragment's end)
-      if (j.stored) out_bytes[q - base] = stored_alloc_bytes(stored_layout((uint32_t)out_bytes[q - base]));
-      seeds[q - base] = (uint32_t)ff_clock_seed();  // `int seed = time(NULL)`, per array
+      if (j.stored) j.out_bytes = stored_alloc_bytes(stored_layout((uint32_t)j.out_bytes));
+      j.seed = (uint32_t)ff_clock_seed();  // `int seed = time(NULL)`, per array
     }
-    alloc_outputs(ctx, jobs, base, end, out_bytes);
+    alloc_outputs(ctx, jobs, chunk_idx);
     for (size_t q = base; q < end; ++q) {
-      FfJob& j = jobs[q];
+      FfWork& j = jobs[q];
       if (!j.stored) continue;
       j.out.bytes = j.elems * (size_t)j.nb;  // the payload; COMPRESSING reads it in the stream layout
       j.out.layout = j.nb == 1 ? kLayoutStored1 : kLayoutStored2;
@@ -321,35 +326,29 @@ void FixingFloatFilter::encode_messages(Context* ctx, std::vector<FfMessage>& ms
       rb->host.assign(4 * (size_t)nlazy, 0u);
       ring_dev = ctx->claim_lazy(rb, nlazy);
     }
-    auto range_of = [&](size_t q) -> float* {
-      const int k = lazy_idx[q - base];
-      return k < 0 ? nullptr : reinterpret_cast<float*>(rb->dev.ptr + 16 * (size_t)k);
+    auto range_of = [&](const FfWork& j) -> float* {
+      return j.lazy_idx < 0 ? nullptr : reinterpret_cast<float*>(rb->dev.ptr + 16 * (size_t)j.lazy_idx);
     };
-    auto ring_of = [&](size_t q) -> float* {
-      const int k = lazy_idx[q - base];
-      return k < 0 ? nullptr : ring_dev + 4 * k;
-    };
+    auto ring_of = [&](const FfWork& j) -> float* { return j.lazy_idx < 0 ? nullptr : ring_dev + 4 * j.lazy_idx; };
     auto one = [&](size_t q) {
-      FfJob& j = jobs[q];
+      FfWork& j = jobs[q];
       if (j.stored) {  // (not batchable after all: plain codes, in the larger buffer)
         j.stored = false;
         j.out.layout = kLayoutPlain;
       }
-      const uint32_t t = tickets[q - base];
-      float* r = range_of(q);
-      int s = ff_encode_launch(j.in.ptr, j.elems, j.type, j.nb, presets[q - base], seeds[q - base], j.out.ptr,
-                               ctx->partials(), r, r ? reinterpret_cast<int*>(r + 2) : nullptr, st, ctx->prof(),
-                               t ? ctx->pub_dev((int)(q - base)) : nullptr, t, ring_of(q));
+      float* r = range_of(j);
+      int s = ff_encode_launch(j.in.ptr, j.elems, j.type, j.nb, j.preset, j.seed, j.out.ptr, ctx->partials(), r,
+                               r ? reinterpret_cast<int*>(r + 2) : nullptr, st, ctx->prof(),
+                               j.ticket ? ctx->pub_dev(j.slot) : nullptr, j.ticket, ring_of(j));
       if (s != kOk) throw CheckError(s, "ff_encode launch failed");
     };
     auto batch = [&](std::vector<size_t>& part) {
       std::vector<FfArray> arrs;
       arrs.reserve(part.size());
       for (size_t q : part) {
-        const FfJob& j = jobs[q];
-        const uint32_t t = tickets[q - base];
-        arrs.push_back(FfArray{j.in.ptr, j.out.ptr, j.elems, presets[q - base], seeds[q - base],
-                               t ? (int)(q - base) : -1, t, range_of(q), ring_of(q), j.stored});
+        const FfWork& j = jobs[q];
+        arrs.push_back(FfArray{j.in.ptr, j.out.ptr, j.elems, j.preset, j.seed, j.ticket ? j.slot : -1, j.ticket,
+                               range_of(j), ring_of(j), j.stored});
       }
       Buffer scratch = ctx->alloc(ff_batch_partials_bytes(arrs.data(), (int)arrs.size()));
       PSF_HPROF(9);
@@ -366,17 +365,17 @@ void FixingFloatFilter::encode_messages(Context* ctx, std::vector<FfMessage>& ms
     for_each_batch(jobs, base, end, true, one, batch);
     if (rb) ctx->track(rb);
     for (size_t q = base; q < end; ++q) {
-      FfJob& j = jobs[q];
-      if (tickets[q - base]) {
-        ctx->wait_ticket((int)(q - base), tickets[q - base]);
-        const Slot& hs = *ctx->pub_host((int)(q - base));
+      FfWork& j = jobs[q];
+      if (j.ticket) {
+        ctx->wait_ticket(j.slot, j.ticket);
+        const Slot& hs = *ctx->pub_host(j.slot);
         if (!j.fp->has_min) j.fp->set_min(hs.range[0]);
         if (!j.fp->has_max) j.fp->set_max(hs.range[1]);
         if (hs.status == kErrHip) ctx->handoff_failed();
         if (hs.status != kOk) throw CheckError(kErrBin, "CHECK_GT(bin, 0)");
-      } else if (lazy_idx[q - base] >= 0) {
+      } else if (j.lazy_idx >= 0) {
         j.fp->pending = rb;
-        j.fp->pending_idx = lazy_idx[q - base];
+        j.fp->pending_idx = j.lazy_idx;
         j.fp->pending_min = !j.fp->has_min;
         j.fp->pending_max = !j.fp->has_max;
       }
@@ -415,7 +414,7 @@ const float* FixedFloatConfig::device_range() const {
 // (only where every filter listed before FIXING_FLOAT is KEY_CACHING, so
 // nothing decoded after it reads values).
 void FixingFloatFilter::decode_messages(Context* ctx, std::vector<FfMessage>& msgs) {
-  std::vector<FfJob> jobs;
+  std::vector<FfWork> jobs;
   jobs.reserve(msgs.size());
   for (auto& m : msgs) {
     const size_t first = jobs.size();
@@ -429,7 +428,7 @@ void FixingFloatFilter::decode_messages(Context* ctx, std::vector<FfMessage>& ms
     std::vector<uint8_t> pre;
     pre.swap(m.msg->predecoded);  // decoded by the COMPRESSING decode before (fused_ff_plan)
     for (size_t q = first; q < jobs.size(); ++q) {
-      FfJob& j = jobs[q];
+      FfWork& j = jobs[q];
       FixedFloatConfig& fp = *j.fp;
       if ((size_t)j.i < pre.size() && pre[j.i]) continue;
       if (fp.pending && fp.pending->ctx == ctx && !fp.pending->done && !(defer && j.type == kFloat)) {
@@ -458,38 +457,21 @@ void FixingFloatFilter::decode_messages(Context* ctx, std::vector<FfMessage>& ms
   }
   if (jobs.empty()) return;
   hipStream_t st = ctx->stream();
-  std::vector<size_t> out_bytes(jobs.size());
-  for (size_t q = 0; q < jobs.size(); ++q) {
-    FfJob& j = jobs[q];
-    j.in = ctx->to_device(j.msg->value[j.i]);
-    j.elems = j.in.bytes / (size_t)j.nb;
-    out_bytes[q] = j.elems * (j.type == kFloat ? 4 : 8);
-  }
   // outputs: the message's destination for the array when it names one of
   // the right size (Message::value_dest), else library memory
   std::vector<size_t> need;
-  std::vector<size_t> need_bytes;
   for (size_t q = 0; q < jobs.size(); ++q) {
-    FfJob& j = jobs[q];
+    FfWork& j = jobs[q];
+    j.in = ctx->to_device(j.msg->value[j.i]);
+    j.elems = j.in.bytes / (size_t)j.nb;
+    j.out_bytes = j.elems * (j.type == kFloat ? 4 : 8);
     const Buffer* d = (size_t)j.i < j.msg->value_dest.size() ? &j.msg->value_dest[j.i] : nullptr;
-    if (d && d->ptr && d->loc == Loc::kDevice && d->bytes == out_bytes[q]) {
-      j.out = *d;
-    } else {
-      need.push_back(q);
-      need_bytes.push_back(out_bytes[q]);
-    }
+    if (d && d->ptr && d->loc == Loc::kDevice && d->bytes == j.out_bytes) j.out = *d;
+    else need.push_back(q);
   }
-  if (need.size() == jobs.size()) {
-    alloc_outputs(ctx, jobs, 0, jobs.size(), out_bytes);
-  } else if (!need.empty()) {
-    std::vector<FfJob> tmp;
-    tmp.reserve(need.size());
-    for (size_t q : need) tmp.push_back(jobs[q]);
-    alloc_outputs(ctx, tmp, 0, tmp.size(), need_bytes);
-    for (size_t t = 0; t < need.size(); ++t) jobs[need[t]].out = tmp[t].out;
-  }
+  if (!need.empty()) alloc_outputs(ctx, jobs, need);
   auto one = [&](size_t q) {
-    FfJob& j = jobs[q];
+    FfWork& j = jobs[q];
     int s = ff_decode_launch(j.in.ptr, j.elems, j.type, j.nb, j.range, j.fp->min_value, j.fp->max_value,
                              j.out.ptr, st, ctx->prof());
     if (s != kOk) throw CheckError(s, "ff_decode launch failed");
@@ -498,7 +480,7 @@ void FixingFloatFilter::decode_messages(Context* ctx, std::vector<FfMessage>& ms
     std::vector<FfDecArray> arrs;
     arrs.reserve(part.size());
     for (size_t q : part) {
-      const FfJob& j = jobs[q];
+      const FfWork& j = jobs[q];
       arrs.push_back(FfDecArray{j.in.ptr, j.out.ptr, j.elems, j.fp->min_value, j.fp->max_value, j.range});
     }
     PSF_HPROF(10);

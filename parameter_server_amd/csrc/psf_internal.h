@@ -154,7 +154,7 @@ inline void psf_launch(F kernel, dim3 grid, dim3 block, uint32_t shm, hipStream_
   }
 }
 
-// ff_codec.hip
+// ff_codec.hip (the launch layer of ff_kernels.h)
 double ff_ratio(int nb);
 int ff_grid(size_t work_items);
 // range_out/status_out: optional device pointers (async API); pub: optional
@@ -191,7 +191,7 @@ struct FfDecArray {
 // A context's state for ff_fused_batch (a small batch's min/max, encode and a
 // pending decode in one launch): a 128-byte line of device counters per array
 // slot, zero between launches (the kernel zeroes what it used)
-constexpr int kFusedArrays = 64;  // = kBatchSmall (ff_codec.hip)
+constexpr int kFusedArrays = 64;  // = kBatchSmall (ff_kernels.h)
 struct FfFusedCtl {
   uint32_t* ctl = nullptr;
   // host-mapped word a workgroup whose hand-off gave up sets to kErrHip

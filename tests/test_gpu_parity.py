@@ -96,6 +96,62 @@ def test_ff_unaligned_and_preset(ctx, port):
         assert dec.cpu().numpy().tobytes() == pd.tobytes()
 
 
+_DISPATCH_N = 2 * 4096 + 3  # two full 1024-group tiles and a ragged tail
+_DISPATCH_SEED = 4242
+_DISPATCH_PRESET = (-1.5, 1.5)
+_dispatch_ref = {}
+
+
+def _dispatch_reference(port, dtype, nb):
+    """The port's codes, range and decoded values of one (dtype, nb), with the
+    computed and with the preset range; shared by the three alignments."""
+    key = (np.dtype(dtype).name, nb)
+    if key not in _dispatch_ref:
+        # one spare element in front: the values are base[1:] in every case
+        base = (np.random.default_rng(1000 + nb).standard_normal(_DISPATCH_N + 1) * 4).astype(dtype)
+        ref = []
+        for a, b in ((None, None), _DISPATCH_PRESET):
+            st, pc, pmn, pmx = port.ff_encode(base[1:], nb, _DISPATCH_SEED, a, b)
+            assert st == 0, (key, a, b)  # CHECK_GT(bin, 0) holds in the port itself (the ratio wraps at nb >= 4)
+            st, pd = port.ff_decode(pc, nb, pmn, pmx, dtype)
+            assert st == 0, (key, a, b)
+            ref.append((a, b, pc, pmn, pmx, pd))
+        for arr in (base, *(r[2] for r in ref), *(r[5] for r in ref)):
+            arr.setflags(write=False)
+        _dispatch_ref[key] = (base, ref)
+    return _dispatch_ref[key]
+
+
+@pytest.mark.parametrize("preset", [False, True], ids=["computed", "preset"])
+@pytest.mark.parametrize("align", ["aligned", "values+1", "codes+1"])
+@pytest.mark.parametrize("nb", [1, 2, 3, 4, 5, 6, 7])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_ff_dispatch_every_type_nb_alignment(ctx, port, dtype, nb, align, preset):
+    """Every (value type, num_bytes) of the single-array encode and decode, on
+    the vector kernels (aligned), on the element-wise encode (values one
+    element off a 16-byte boundary) and on the element-wise decode (codes one
+    byte off), with the computed and with a preset range: codes, range bits
+    and decoded bytes equal the port's."""
+    base, ref = _dispatch_reference(port, dtype, nb)
+    a, b, pc, pmn, pmx, pd = ref[int(preset)]
+    if align == "values+1":
+        xt = torch.from_numpy(base.copy()).to(DEV)[1:]
+        assert xt.data_ptr() % 16 != 0
+    else:
+        xt = torch.from_numpy(base[1:].copy()).to(DEV)
+        assert xt.data_ptr() % 16 == 0
+    codes, mn, mx = ctx.ff_encode(xt, nb, _DISPATCH_SEED, a, b)
+    assert _bits(mn) == _bits(pmn) and _bits(mx) == _bits(pmx)
+    assert np.array_equal(codes.cpu().numpy(), pc)
+    if align == "codes+1":
+        buf = torch.zeros(codes.numel() + 1, dtype=torch.uint8, device=DEV)
+        buf[1:] = codes
+        codes = buf[1:]
+        assert codes.data_ptr() % 4 == 1
+    dec = ctx.ff_decode(codes, nb, mn, mx, dtype=xt.dtype)
+    assert dec.cpu().numpy().tobytes() == pd.tobytes()
+
+
 def test_ff_async_device_range(ctx, port):
     n = 1 << 18
     x = torch.randn(n, device=DEV)

@@ -109,7 +109,7 @@ def test_minmax_tie_rule(port):
 
 def test_fast_floor_guard_is_sound():
     """The HIP encoder skips the f64 division when d*(ratio/bin) is farther
-    than 2^-26 from an integer (ff_codec.hip quant_floor).  Check, in IEEE
+    than 2^-26 from an integer (ff_kernels.h quant_floor).  Check, in IEEE
     double without FMA (numpy), that the guard never lets a floor differ from
     the reference's floor(d / bin * ratio)."""
     rng = np.random.default_rng(0)
@@ -139,7 +139,7 @@ def test_fast_floor_guard_is_sound():
 
 
 def test_fast_floor_f32_guard_is_sound():
-    """The f32 / num_bytes=1 encoder (ff_codec.hip encode_tile_f32_nb1)
+    """The f32 / num_bytes=1 encoder (ff_kernels.h encode_tile_f32_nb1)
     computes t = (med3(x, min, max) - min) * float(ratio / bin) in float32 and
     takes floor(t) when frac(t) is farther than 2^-14 from an integer (tested
     on the u32 bit pattern of frac); numpy float32 arithmetic (IEEE, no FMA)
@@ -290,7 +290,7 @@ def test_snappy_port_vs_libsnappy_random(port):
 @pytest.mark.parametrize("nb", [1, 2, 3])
 def test_decode_quotient(port, nb):
     """The device decode forms r / ratio as fma(fma(-q0, ratio, r), inv, q0)
-    with q0 = r * inv, inv = RN(1/ratio) (ff_codec.hip dequant_q); it must
+    with q0 = r * inv, inv = RN(1/ratio) (ff_kernels.h dequant_q); it must
     equal the IEEE quotient of fixing_float.h:97 for every possible code."""
     assert port.decode_quotient_mismatches(nb) == 0
 

@@ -1,12 +1,15 @@
-// C3-shape probe of the REAL single-array FIXING_FLOAT kernels: includes
-// ff_codec.hip and calls ff_encode_launch (min/max pass + encode) and
-// ff_decode_launch on 10M f32 values, 3 rotating arrays, like bench.py's C3
-// step minus KEY_CACHING.  Variants of the kernels are A/B'd by building this
-// file with different -D flags; run under `rocprofv3 --kernel-trace --stats`.
+// C3-shape probe of the REAL single-array FIXING_FLOAT kernels: the kernels
+// of ff_kernels.h (ff_minmax_partials is launched directly in mode 1) and, for
+// ff_encode_launch (min/max pass + encode), ff_decode_launch and the LCG bit
+// table, their launch layer ff_codec.hip, compiled into this program, on 10M
+// f32 values, 3 rotating arrays, like bench.py's C3 step minus KEY_CACHING.
+// Variants of the kernels are A/B'd by building this file with different -D
+// flags; run under `rocprofv3 --kernel-trace --stats`.
 //   argv: iters data(0 randn, 1 grid values in [-4, 4)) pub(0/1)
 // Build: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -I include \
 //          -I parameter_server_amd/csrc -o tools/c3real_probe tools/c3real_probe.hip
-#include "../parameter_server_amd/csrc/ff_codec.hip"
+#include "../parameter_server_amd/csrc/ff_kernels.h"
+#include "../parameter_server_amd/csrc/ff_codec.hip"  // the launchers: this is their only other translation unit
 
 #include <math.h>
 #include <algorithm>
