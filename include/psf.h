@@ -314,18 +314,27 @@ int psf_ff_decode_match(psf_context* ctx, const uint64_t* d_src_key, size_t nsrc
 int psf_msg_ordered_match(psf_context* ctx, const psf_message* msg, int i, const uint64_t* d_dst_key,
                           size_t ndst, void* d_dst_val, int k, int value_type, int op, size_t* n);
 
-/* KVMap<Key, float, FTRLEntry, SGDState> (src/parameter/kv_map.h:32-91,
- * src/app/linear_method/async_sgd.h:42-154): the async-SGD server's model as a
- * hash table in HBM (grows 2x on the device at load 1/2).  lr_type 1 CONSTANT /
- * 2 DECAY with alpha, beta (LearningRateConfig, linear.proto:93-101); penalty
- * ElasticNet(lambda1, lambda2) (penalty.h:41-91: L1 = (lambda[0], lambda[1] or
- * 0), L2 = (0, lambda[0])).  CHECKs of LearningRate / ElasticNet ->
- * PSF_ERR_CHECK.  `capacity` = expected number of keys (a hint). */
+/* KVMap<Key, float, Entry, SGDState> (src/parameter/kv_map.h:32-117,
+ * src/app/linear_method/async_sgd.h:42-176): the async-SGD server's model as a
+ * hash table in HBM (grows 2x on the device at load 1/2).  Entry is the
+ * server's FTRLEntry (PSF_KVMAP_FTRL, async_sgd.h:132-154) or AdaGradEntry
+ * (PSF_KVMAP_ADAGRAD, async_sgd.h:159-176); both read the same SGDState:
+ * lr_type 1 CONSTANT / 2 DECAY with alpha, beta (LearningRateConfig,
+ * linear.proto:93-101); penalty ElasticNet(lambda1, lambda2) (penalty.h:41-91:
+ * L1 = (lambda[0], lambda[1] or 0), L2 = (0, lambda[0])).  (The reference's
+ * AdaGrad branch forgets set_state, async_sgd.h:54-56; the state here is the
+ * one its FTRL branch sets.)  CHECKs of LearningRate / ElasticNet ->
+ * PSF_ERR_CHECK.  `capacity` = expected number of keys (a hint).
+ * psf_kvmap_create makes an FTRL map; an unknown algo -> PSF_ERR_ARG. */
+#define PSF_KVMAP_FTRL 0
+#define PSF_KVMAP_ADAGRAD 1
 typedef struct psf_kvmap psf_kvmap;
 int psf_kvmap_create(psf_context* ctx, size_t capacity, int lr_type, double alpha, double beta,
                      double lambda1, double lambda2, psf_kvmap** out);
+int psf_kvmap_create_algo(psf_context* ctx, size_t capacity, int algo, int lr_type, double alpha, double beta,
+                          double lambda1, double lambda2, psf_kvmap** out);
 int psf_kvmap_destroy(psf_kvmap* map);
-/* KVMap::SetValue on a push message: FTRLEntry::Set for every key (pending
+/* KVMap::SetValue on a push message: the entry's Set for every key (pending
  * FIXING_FLOAT codes dequantised in-register).  Asynchronous; a failed
  * CHECK_GT(eta, 0) is reported by the next psf_kvmap_stats. */
 int psf_kvmap_set_value(psf_kvmap* map, const psf_message* msg);
@@ -339,6 +348,25 @@ int psf_kvmap_pull(psf_kvmap* map, const uint64_t* d_keys, size_t n, float* d_w)
  * serially in float); size = stored keys.  Synchronous. */
 int psf_kvmap_stats(psf_kvmap* map, int64_t* nnz, double* weight_sum, double* delta_sum,
                     uint64_t* size);
+/* The model as KVMap::WriteToFile enumerates it (kv_map.h:113-117): every
+ * (key, w) with w != 0 into the device arrays d_keys / d_w of `cap` elements,
+ * in no particular order (the reference iterates an unordered_map).  *n = the
+ * number of such entries.  If *n > cap: PSF_ERR_ARG with *n set; the first
+ * `cap` positions may be written and nothing beyond them.  cap == 0 is the
+ * size query: the pointers may be null, nothing is written, and the call
+ * returns PSF_OK with *n.  A pending push failure is reported as
+ * by psf_kvmap_stats.  Synchronous. */
+int psf_kvmap_export(psf_kvmap* map, uint64_t* d_keys, float* d_w, size_t cap, size_t* n);
+/* WriteToFile's text format from host arrays (no GPU): one "key \t w \n" line
+ * per pair with w != 0 -- the key in decimal, the weight as `std::ostream <<
+ * float` prints it (precision 6, i.e. %g).  sorted != 0: lines by ascending
+ * key; else in input order.  Creates the parent directory if absent.  An I/O
+ * failure -> PSF_ERR_ARG with the reason in psf_last_error. */
+int psf_model_write_text(const char* path, const uint64_t* keys, const float* w, size_t n, int sorted);
+/* KVMap::WriteToFile (kv_map.h:99-117): psf_kvmap_export, a copy to the host,
+ * psf_model_write_text.  *n_written (optional) = lines written.
+ * (The reference's USE_S3 upload branch is not built.) */
+int psf_kvmap_write_file(psf_kvmap* map, const char* path, int sorted, size_t* n_written);
 
 /* ---- many messages at once --------------------------------------------
  * RemoteNode::EncodeMessage / DecodeMessage of n messages, message i on

@@ -120,6 +120,8 @@ SIGNATURES = {
                               C.c_int),
     "psf_kvmap_create": ([vp, sz, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(vp)],
                          C.c_int),
+    "psf_kvmap_create_algo": ([vp, sz, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                               C.POINTER(vp)], C.c_int),
     "psf_kvmap_destroy": ([vp], C.c_int),
     "psf_kvmap_set_value": ([vp, vp], C.c_int),
     "psf_kvmap_get_value": ([vp, vp], C.c_int),
@@ -127,6 +129,9 @@ SIGNATURES = {
     "psf_kvmap_pull": ([vp, vp, sz, vp], C.c_int),
     "psf_kvmap_stats": ([vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
                          C.POINTER(u64)], C.c_int),
+    "psf_kvmap_export": ([vp, vp, vp, sz, C.POINTER(sz)], C.c_int),
+    "psf_model_write_text": ([C.c_char_p, vp, vp, sz, C.c_int], C.c_int),
+    "psf_kvmap_write_file": ([vp, C.c_char_p, C.c_int, C.POINTER(sz)], C.c_int),
     "psf_nodes_encode": ([C.POINTER(vp), C.POINTER(vp), C.c_int], C.c_int),
     "psf_nodes_decode": ([C.POINTER(vp), C.POINTER(vp), C.c_int], C.c_int),
     "psf_nodes_roundtrip": ([C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int], C.c_int),
@@ -178,7 +183,8 @@ SIGNATURES = {
 
 KERNELS = ("ff_minmax_partials", "ff_encode", "ff_decode", "crc32c_chunks", "noise_add",
            "snappy_compress", "snappy_decompress", "ordered_match", "kvmap_push", "kvmap_get",
-           "ff_decode_minmax", "ff_minmax_encode")
+           "ff_decode_minmax", "ff_minmax_encode", "kvmap_export")
+KVMAP_FTRL, KVMAP_ADAGRAD = 0, 1
 OP_ASSIGN, OP_PLUS, OP_MINUS, OP_TIMES, OP_DIVIDE = 0, 1, 2, 3, 4
 
 _lib = None

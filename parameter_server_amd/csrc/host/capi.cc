@@ -24,7 +24,7 @@
 struct psf_context { psf::Context* impl; };
 struct psf_node { psf::RemoteNode* impl; };
 struct psf_message { psf::Message m; };
-struct psf_kvmap { psf::KvMapFtrl* impl; psf::Context* ctx; };
+struct psf_kvmap { psf::KvMap* impl; psf::Context* ctx; };
 
 namespace {
 thread_local std::string g_last_error;
@@ -1234,7 +1234,8 @@ int psf_profile_read(psf_context* ctx, int k, int64_t* launches, double* total_m
 const char* psf_profile_kernel_name(int k) {
   static const char* names[] = {"ff_minmax_partials", "ff_encode", "ff_decode", "crc32c_chunks",
                                 "noise_add", "snappy_compress", "snappy_decompress", "ordered_match",
-                                "kvmap_push", "kvmap_get", "ff_decode_minmax", "ff_minmax_encode"};
+                                "kvmap_push", "kvmap_get", "ff_decode_minmax", "ff_minmax_encode",
+                                "kvmap_export"};
   static_assert(sizeof(names) / sizeof(names[0]) == psf::kKNum, "one name per kernel id");
   return (k >= 0 && k < psf::kKNum) ? names[k] : "?";
 }
@@ -1311,24 +1312,33 @@ int psf_msg_ordered_match(psf_context* ctx, const psf_message* msg, int i, const
     return PSF_OK;
   });
 }
-int psf_kvmap_create(psf_context* ctx, size_t capacity, int lr_type, double alpha, double beta,
-                     double lambda1, double lambda2, psf_kvmap** out) {
+int psf_kvmap_create_algo(psf_context* ctx, size_t capacity, int algo, int lr_type, double alpha, double beta,
+                          double lambda1, double lambda2, psf_kvmap** out) {
   return guarded(ctx ? ctx->impl : nullptr, [&] {
     if (!ctx || !out || (lr_type != 1 && lr_type != 2)) return PSF_ERR_ARG;
-    psf::FtrlConfig c;
+    if (algo != PSF_KVMAP_FTRL && algo != PSF_KVMAP_ADAGRAD) {
+      g_last_error = "psf_kvmap_create_algo: unknown algo";
+      return PSF_ERR_ARG;
+    }
+    psf::KvMapConfig c;
+    c.algo = algo;
     c.lr_type = lr_type;
     c.alpha = alpha;
     c.beta = beta;
     c.lambda1 = lambda1;
     c.lambda2 = lambda2;
-    *out = new psf_kvmap{new psf::KvMapFtrl(ctx->impl, capacity, c), ctx->impl};
+    *out = new psf_kvmap{new psf::KvMap(ctx->impl, capacity, c), ctx->impl};
     psf::Context::ref(ctx->impl);
     return PSF_OK;
   });
 }
+int psf_kvmap_create(psf_context* ctx, size_t capacity, int lr_type, double alpha, double beta,
+                     double lambda1, double lambda2, psf_kvmap** out) {
+  return psf_kvmap_create_algo(ctx, capacity, PSF_KVMAP_FTRL, lr_type, alpha, beta, lambda1, lambda2, out);
+}
 int psf_kvmap_destroy(psf_kvmap* map) {
   if (!map) return PSF_OK;
-  psf::KvMapFtrl::unref(map->impl);  // (drops the context reference with the map)
+  psf::KvMap::unref(map->impl);  // (drops the context reference with the map)
   delete map;
   return PSF_OK;
 }
@@ -1363,11 +1373,36 @@ int psf_kvmap_pull(psf_kvmap* map, const uint64_t* d_keys, size_t n, float* d_w)
 int psf_kvmap_stats(psf_kvmap* map, int64_t* nnz, double* weight_sum, double* delta_sum, uint64_t* size) {
   return guarded(map ? map->ctx : nullptr, [&] {
     if (!map) return PSF_ERR_ARG;
-    const psf::KvMapFtrl::Stats s = map->impl->stats();
+    const psf::KvMap::Stats s = map->impl->stats();
     if (nnz) *nnz = s.nnz;
     if (weight_sum) *weight_sum = s.weight_sum;
     if (delta_sum) *delta_sum = s.delta_sum;
     if (size) *size = s.size;
+    return PSF_OK;
+  });
+}
+int psf_kvmap_export(psf_kvmap* map, uint64_t* d_keys, float* d_w, size_t cap, size_t* n) {
+  return guarded(map ? map->ctx : nullptr, [&] {
+    if (!map || !n || (cap && (!d_keys || !d_w))) return PSF_ERR_ARG;
+    map->impl->export_nonzero(d_keys, d_w, cap, n);
+    if (cap && *n > cap) {  // (cap == 0 is the size query)
+      g_last_error = "psf_kvmap_export: " + std::to_string(*n) + " entries, room for " + std::to_string(cap);
+      return PSF_ERR_ARG;
+    }
+    return PSF_OK;
+  });
+}
+int psf_model_write_text(const char* path, const uint64_t* keys, const float* w, size_t n, int sorted) {
+  return guarded([&] {
+    psf::model_write_text(path, keys, w, n, sorted != 0);
+    return PSF_OK;
+  });
+}
+int psf_kvmap_write_file(psf_kvmap* map, const char* path, int sorted, size_t* n_written) {
+  return guarded(map ? map->ctx : nullptr, [&] {
+    if (!map || !path) return PSF_ERR_ARG;
+    const size_t lines = map->impl->write_file(path, sorted != 0);
+    if (n_written) *n_written = lines;
     return PSF_OK;
   });
 }

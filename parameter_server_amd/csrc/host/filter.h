@@ -156,7 +156,7 @@ class RemoteNode {
   Filter* FindFilterOrCreate(const FilterConfig& conf);
   Context* ctx() const { return ctx_; }
   // Server side: let FIXING_FLOAT's decode hand its codes to the consumer
-  // (KvMapFtrl / ordered match dequantise them in-register).
+  // (KvMap / ordered match dequantise them in-register).
   void set_defer_dequant(bool v);
   bool defer_dequant() const { return defer_dequant_; }
 

@@ -21,7 +21,7 @@ PushRouter::~PushRouter() {
   pend_.finish();
   pend_dec_.finish();
   Exchange::unref(ex_);
-  KvMapFtrl::unref(store_);
+  KvMap::unref(store_);
 }
 
 // The key width SliceKOFVMessage<K> slices with (message.h:107-147): the

@@ -101,12 +101,12 @@ class PushRouter {
   // so the match is the run's offset; the FIXING_FLOAT decode writes there
   // directly).
   // store: the KVMap of this rank's servers (the router holds a reference)
-  void set_store(KvMapFtrl* store) {
-    KvMapFtrl::ref(store);
-    KvMapFtrl::unref(store_);
+  void set_store(KvMap* store) {
+    KvMap::ref(store);
+    KvMap::unref(store_);
     store_ = store;
   }
-  KvMapFtrl* store() const { return store_; }
+  KvMap* store() const { return store_; }
   // one whole pull step: through the native exchange (any world), or all
   // local (world 1 without loopback)
   // prefetch_next: queue the next pull's slicing of the same requests on the
@@ -160,7 +160,7 @@ class PushRouter {
 
   Context* ctx_;
   Exchange* ex_ = nullptr;
-  KvMapFtrl* store_ = nullptr;
+  KvMap* store_ = nullptr;
   std::vector<KeyRange> ranges_;
   int rank_, world_;
   bool loopback_;

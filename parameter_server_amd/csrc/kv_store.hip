@@ -10,11 +10,13 @@
 //                   (src/parameter/kv_vector.h:182-183,205-207,237): for every
 //                   src key also in dst (both sorted),
 //                   dst_val[j*k+i] op= src_val[s*k+i].
-//   kvmap_*         KVMap<Key, float, FTRLEntry, SGDState>
-//                   (src/parameter/kv_map.h:69-91,
-//                   src/app/linear_method/async_sgd.h:89-154): the async-SGD
+//   kvmap_*         KVMap<Key, float, FTRLEntry | AdaGradEntry, SGDState>
+//                   (src/parameter/kv_map.h:69-117,
+//                   src/app/linear_method/async_sgd.h:89-176): the async-SGD
 //                   server's model as an open-addressing hash table in HBM;
-//                   SetValue = FTRLEntry::Set per key, GetValue = w per key.
+//                   SetValue = Entry::Set per key, GetValue = w per key,
+//                   WriteToFile's enumeration = a stream compaction of the
+//                   table (kvmap_export_kernel).
 //
 // Compiled with -ffp-contract=off like every codec file: the reference's float
 // expressions are evaluated operation by operation (g++/x86-64 SSE, no FMA).
@@ -270,14 +272,19 @@ int ordered_match_launch(const uint64_t* src_key, size_t nsrc, const void* src_v
                               : launch_match<double, false>(p, st, prof);
 }
 
-// --------------------------------------------------- KVMap (FTRL) ---------
+// ------------------------------------------- KVMap (FTRL / AdaGrad) -------
 // Slot layout: 32 B, so the probe and the entry it finds share one cache line
 // (4 slots per 128 B line).  key == kEmptyKey marks a free slot (the key
 // 2^64-1 lies outside every server range: Range::All() is [0, 2^64-1),
-// range.h:92-95).  A free slot's payload is zero = FTRLEntry's default state.
+// range.h:92-95).  A free slot's payload is zero = the default state of
+// FTRLEntry and of AdaGradEntry.  Both entries keep their weight in `w`, so
+// the get, rehash and export kernels serve either algorithm; an AdaGrad map
+// keeps sum_sq_grad in `sqrt_n` and leaves `z` 0.
 struct alignas(32) KvSlot {
   unsigned long long key;
-  float w, z, sqrt_n, pad;
+  float w, z;
+  float sqrt_n;  // FTRLEntry::sqrt_n / AdaGradEntry::sum_sq_grad
+  float pad;
   float pad2[2];
 };
 static_assert(sizeof(KvSlot) == 32, "slot size");
@@ -299,7 +306,7 @@ struct FtrlParams {
 };
 
 // SGDState counters (async_sgd.h:118-125) plus table bookkeeping; mirrored by
-// KvMapFtrl::Stats on the host.
+// KvMap::Stats on the host.
 struct KvStats {
   long long nnz_delta;
   double weight_sum, delta_sum;
@@ -308,9 +315,24 @@ struct KvStats {
   int pad;
 };
 
-// FTRLEntry::Set (async_sgd.h:137-151) with LearningRate::eval
-// (learning_rate.h:15-22) and ElasticNet::proximal (penalty.h:51-56), float
-// arithmetic one operation at a time.
+// LearningRate::eval (learning_rate.h:15-22): DECAY alpha / (x + beta), else
+// CONSTANT alpha.
+__device__ __forceinline__ float lr_eval(const FtrlParams& f, float x) {
+  return f.lr_decay ? f.alpha / (x + f.beta) : f.alpha;
+}
+
+// ElasticNet::proximal(z, eta) (penalty.h:51-56), float arithmetic one
+// operation at a time; bad_eta collects CHECK_GT(eta, 0) (penalty.h:52).
+__device__ __forceinline__ float elastic_proximal(float zz, float eta, const FtrlParams& f, int& bad_eta) {
+  bad_eta |= !(eta > 0.0f) ? 1 : 0;
+  const float leta = f.lambda1 * eta;
+  if (zz <= leta && zz >= -leta) return 0.0f;
+  const float den = 1.0f + f.lambda2 * eta;
+  return zz > 0.0f ? (zz - leta) / den : (zz + leta) / den;
+}
+
+// FTRLEntry::Set (async_sgd.h:137-151), float arithmetic one operation at a
+// time.  Returns the old weight for SGDState::UpdateWeight.
 __device__ __forceinline__ float ftrl_set(KvSlot& e, float grad, const FtrlParams& f, int& bad_eta) {
   const float w_old = e.w;
   const float sn = e.sqrt_n;
@@ -319,19 +341,32 @@ __device__ __forceinline__ float ftrl_set(KvSlot& e, float grad, const FtrlParam
   const float sigma = (sqrt_n_new - sn) / f.alpha;
   const float t = grad - sigma * w_old;
   const float z = e.z + t;
-  const float eta = f.lr_decay ? f.alpha / (sqrt_n_new + f.beta) : f.alpha;
+  const float eta = lr_eval(f, sqrt_n_new);
   const float zz = -z * eta;  // proximal(-z*eta, eta)
-  bad_eta |= !(eta > 0.0f) ? 1 : 0;  // CHECK_GT(eta, 0), penalty.h:52
-  const float leta = f.lambda1 * eta;
-  float w;
-  if (zz <= leta && zz >= -leta) {
-    w = 0.0f;
-  } else {
-    const float den = 1.0f + f.lambda2 * eta;
-    w = zz > 0.0f ? (zz - leta) / den : (zz + leta) / den;
-  }
+  const float w = elastic_proximal(zz, eta, f, bad_eta);
   e.z = z;
   e.sqrt_n = sqrt_n_new;
+  e.w = w;
+  return w_old;
+}
+
+// AdaGradEntry::Set (async_sgd.h:159-171).  The reference's unqualified sqrt
+// may resolve to the double overload; the square root is correctly rounded in
+// both widths and double carries more than 2 * 24 + 2 bits, so rounding the
+// double result to float gives the bits of sqrtf: nothing depends on which
+// overload it is.
+// The reference's AdaGrad branch never calls set_state (async_sgd.h:54-56
+// against :50-52), so its st->lr is null and the first Set would crash; this
+// builds what it plainly intends, the SGDState(penalty, learning_rate) the
+// FTRL branch sets (a documented divergence).
+__device__ __forceinline__ float adagrad_set(KvSlot& e, float grad, const FtrlParams& f, int& bad_eta) {
+  const float g2 = grad * grad;
+  const float ss = e.sqrt_n + g2;  // sum_sq_grad += grad * grad
+  const float eta = lr_eval(f, __builtin_sqrtf(ss));
+  const float w_old = e.w;
+  const float step = eta * grad;
+  const float w = elastic_proximal(w_old - step, eta, f, bad_eta);
+  e.sqrt_n = ss;
   e.w = w;
   return w_old;
 }
@@ -347,7 +382,7 @@ struct KvPushParams {
   KvStats* stats;
 };
 
-template <bool kCodes>
+template <bool kCodes, int kAlgo>
 __global__ __launch_bounds__(kBlock) void kvmap_push_kernel(KvPushParams p) {
   __shared__ float s_lut[256];
   if (kCodes && p.codes.nb == 1) {  // the decode's 256-entry table, same formula
@@ -379,7 +414,7 @@ __global__ __launch_bounds__(kBlock) void kvmap_push_kernel(KvPushParams p) {
       h = (h + 1) & p.mask;
     }
     if (!e) { full = 1; continue; }
-    const float w_old = ftrl_set(*e, g, p.f, bad);
+    const float w_old = kAlgo == kKvAdaGrad ? adagrad_set(*e, g, p.f, bad) : ftrl_set(*e, g, p.f, bad);
     const float w_new = e->w;
     // SGDState::UpdateWeight (async_sgd.h:106-116)
     if (w_new == 0.0f && w_old != 0.0f) --nnz;
@@ -524,6 +559,79 @@ __global__ __launch_bounds__(kBlock) void kvmap_rehash_kernel(const KvSlot* __re
   }
 }
 
+// KVMap::WriteToFile's enumeration (kv_map.h:113-117) as a stream compaction:
+// every slot with key != kEmptyKey and w != 0 (a NaN weight is "not zero", as
+// in `v != 0`, kv_map.h:116; key 0 is a valid key) goes to the dense arrays
+// keys[] / w[], in whatever order the cursor's atomics give (the reference
+// iterates an unordered_map).
+//
+// A workgroup takes tiles of kExportTile slots.  A lane reads the first 16
+// bytes of its kExportPer slots ({key, w, z} as one uint4, as
+// kvmap_get_batch_kernel does), all loads in flight before the first is used.
+// Each keep flag goes to a 64-bit ballot; a lane's position inside its wave is
+// the popcount of the lower lanes, the waves' totals meet in LDS, and one
+// returning device-scope atomicAdd per tile reserves the tile's range on the
+// single output cursor.
+// Tile size: one word takes about 88 returning adds per us, and a 2^24-slot
+// table (512 MiB) streams in about 100 us at the 6.29 TB/s streaming ceiling,
+// which leaves room for about 8800 adds, one per 1900 slots -- hence at least
+// 2048 slots per add.  (Derived from those two figures, not measured.)
+// Every store is guarded by pos < cap_out while the cursor keeps counting, so
+// the host learns the size it needs and nothing is written out of bounds
+// whatever the caller passes.
+constexpr int kExportPer = 8;
+constexpr int kExportTile = kBlock * kExportPer;
+static_assert(kExportTile >= 2048, "slots per cursor add");
+__global__ __launch_bounds__(kBlock) void kvmap_export_kernel(const KvSlot* __restrict__ table, uint64_t nslots,
+                                                              unsigned long long* __restrict__ out_keys,
+                                                              float* __restrict__ out_w, uint64_t cap_out,
+                                                              unsigned long long* cursor) {
+  __shared__ unsigned s_wave[kBlock / 64];
+  __shared__ unsigned long long s_base;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long below = (1ull << lane) - 1;
+  for (uint64_t base = (uint64_t)blockIdx.x * kExportTile; base < nslots; base += (uint64_t)gridDim.x * kExportTile) {
+    uint4 sl[kExportPer];
+#pragma unroll
+    for (int u = 0; u < kExportPer; ++u) {
+      const uint64_t i = base + (uint64_t)u * kBlock + threadIdx.x;
+      sl[u] = make_uint4(~0u, ~0u, 0u, 0u);  // past the table: an empty slot
+      if (i < nslots) sl[u] = *reinterpret_cast<const uint4*>(&table[i]);
+    }
+    unsigned pos[kExportPer];  // position inside this wave's part of the tile
+    unsigned wave_n = 0;
+#pragma unroll
+    for (int u = 0; u < kExportPer; ++u) {
+      const unsigned long long key = (unsigned long long)sl[u].x | ((unsigned long long)sl[u].y << 32);
+      const bool keep = key != kEmptyKey && __uint_as_float(sl[u].z) != 0.0f;
+      const unsigned long long b = __ballot(keep);
+      pos[u] = keep ? wave_n + (unsigned)__popcll(b & below) : ~0u;
+      wave_n += (unsigned)__popcll(b);
+    }
+    if (lane == 0) s_wave[wave] = wave_n;
+    __syncthreads();
+    unsigned before = 0, total = 0;
+#pragma unroll
+    for (int v = 0; v < kBlock / 64; ++v) {
+      const unsigned c = s_wave[v];
+      before += v < wave ? c : 0u;
+      total += c;
+    }
+    if (threadIdx.x == 0) s_base = total ? atomicAdd(cursor, (unsigned long long)total) : 0ull;
+    __syncthreads();
+    const unsigned long long first = s_base + before;
+#pragma unroll
+    for (int u = 0; u < kExportPer; ++u) {
+      if (pos[u] == ~0u) continue;
+      const unsigned long long o = first + pos[u];
+      if (o < cap_out) {
+        out_keys[o] = (unsigned long long)sl[u].x | ((unsigned long long)sl[u].y << 32);
+        out_w[o] = __uint_as_float(sl[u].z);
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void kvmap_init_kernel(KvSlot* t, size_t n) {
   const size_t stride = (size_t)gridDim.x * kBlock;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
@@ -551,10 +659,17 @@ int kvmap_rehash_launch(const void* from, size_t nfrom, void* to, size_t cap_to,
   return launch_status();
 }
 
-int kvmap_push_launch(void* table, size_t cap, const uint64_t* keys, size_t n, const float* grad,
+template <int kAlgo>
+static void launch_push(const KvPushParams& p, bool codes, hipStream_t st) {
+  if (codes) hipLaunchKernelGGL((kvmap_push_kernel<true, kAlgo>), dim3(grid_for(p.n)), dim3(kBlock), 0, st, p);
+  else hipLaunchKernelGGL((kvmap_push_kernel<false, kAlgo>), dim3(grid_for(p.n)), dim3(kBlock), 0, st, p);
+}
+
+int kvmap_push_launch(int algo, void* table, size_t cap, const uint64_t* keys, size_t n, const float* grad,
                       const void* code, int nb, float mn, float mx, float alpha, float beta,
                       int lr_decay, float lambda1, float lambda2, void* stats, hipStream_t st,
                       Profiler* prof) {
+  if (algo != kKvFtrl && algo != kKvAdaGrad) return kErrArg;
   if (n == 0) return kOk;
   KvPushParams p{};
   p.table = static_cast<KvSlot*>(table);
@@ -571,10 +686,22 @@ int kvmap_push_launch(void* table, size_t cap, const uint64_t* keys, size_t n, c
     if (nb <= 0 || nb >= 8) return kErrNbytes;
     p.codes = CodeSrc{static_cast<const uint8_t*>(code), nb, ff_ratio(nb), (double)mx - (double)mn,
                       (double)mn};
-    hipLaunchKernelGGL(kvmap_push_kernel<true>, dim3(grid_for(n)), dim3(kBlock), 0, st, p);
-  } else {
-    hipLaunchKernelGGL(kvmap_push_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, st, p);
   }
+  if (algo == kKvAdaGrad) launch_push<kKvAdaGrad>(p, code != nullptr, st);
+  else launch_push<kKvFtrl>(p, code != nullptr, st);
+  return launch_status();
+}
+
+int kvmap_export_launch(const void* table, size_t cap, uint64_t* out_keys, float* out_w, size_t cap_out,
+                        unsigned long long* d_cursor, hipStream_t st, Profiler* prof, bool* profiled) {
+  // the table read; the host adds the n * 12 bytes written once it knows n
+  ProfScope ps(prof, kKKvExport, st, (double)cap * 32.0);
+  if (profiled) *profiled = ps.p != nullptr;
+  const size_t tiles = (cap + kExportTile - 1) / kExportTile;
+  const unsigned grid = (unsigned)std::min<size_t>(std::max<size_t>(tiles, 1), (size_t)kMaxGrid);
+  hipLaunchKernelGGL(kvmap_export_kernel, dim3(grid), dim3(kBlock), 0, st, static_cast<const KvSlot*>(table),
+                     (uint64_t)cap, reinterpret_cast<unsigned long long*>(out_keys), out_w, (uint64_t)cap_out,
+                     d_cursor);
   return launch_status();
 }
 

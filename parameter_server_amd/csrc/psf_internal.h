@@ -82,7 +82,8 @@ __device__ __forceinline__ void publish_crc(PubSlot* s, uint32_t crc, uint32_t t
 // Kernel launch profiler: HIP events recorded on the launch stream around
 // each kernel, plus the kernel's algorithmic HBM bytes.
 enum KernelId { kKMinmax = 0, kKEncode, kKDecode, kKCrc, kKNoise, kKSnappyCompress,
-                kKSnappyDecompress, kKMatch, kKKvPush, kKKvGet, kKDecodeMinmax, kKFused, kKNum };
+                kKSnappyDecompress, kKMatch, kKKvPush, kKKvGet, kKDecodeMinmax, kKFused,
+                kKKvExport, kKNum };
 class Profiler {
  public:
   ~Profiler();
@@ -433,10 +434,18 @@ size_t kvmap_slot_bytes();
 size_t kvmap_stats_bytes();
 int kvmap_init_launch(void* table, size_t cap, hipStream_t st);
 int kvmap_rehash_launch(const void* from, size_t nfrom, void* to, size_t cap_to, hipStream_t st);
-int kvmap_push_launch(void* table, size_t cap, const uint64_t* keys, size_t n, const float* grad,
+// the map's entry type (PSF_KVMAP_FTRL / PSF_KVMAP_ADAGRAD in include/psf.h)
+constexpr int kKvFtrl = 0;
+constexpr int kKvAdaGrad = 1;
+int kvmap_push_launch(int algo, void* table, size_t cap, const uint64_t* keys, size_t n, const float* grad,
                       const void* code, int nb, float mn, float mx, float alpha, float beta,
                       int lr_decay, float lambda1, float lambda2, void* stats, hipStream_t st,
                       Profiler* prof);
+// Every (key, w) with w != 0 into out_keys / out_w, at most cap_out of them;
+// *d_cursor (zero at launch) ends as their number, which may exceed cap_out.
+// *profiled: whether the profiler timed this launch.
+int kvmap_export_launch(const void* table, size_t cap, uint64_t* out_keys, float* out_w, size_t cap_out,
+                        unsigned long long* d_cursor, hipStream_t st, Profiler* prof, bool* profiled);
 int kvmap_get_launch(const void* table, size_t cap, const uint64_t* keys, size_t n, float* out,
                      hipStream_t st, Profiler* prof);
 // GetValue of many key arrays in one launch: job j looks up keys[0, n) into

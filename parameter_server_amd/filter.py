@@ -213,14 +213,21 @@ class Context:
 
 
 class KVMap:
-    """KVMap<Key, float, FTRLEntry, SGDState> in HBM (kv_map.h:32-91,
-    async_sgd.h:42-154)."""
+    """KVMap<Key, float, FTRLEntry | AdaGradEntry, SGDState> in HBM
+    (kv_map.h:32-117, async_sgd.h:42-176); `algo` is "ftrl" or "adagrad"."""
+
+    ALGOS = {"ftrl": 0, "adagrad": 1}  # PSF_KVMAP_FTRL / PSF_KVMAP_ADAGRAD
 
     def __init__(self, ctx: Context, capacity=1 << 20, lr_type=2, alpha=0.01, beta=10.0, lambda1=0.0,
-                 lambda2=0.0):
+                 lambda2=0.0, algo="ftrl"):
+        if algo not in self.ALGOS:
+            raise ValueError(f"KVMap algo must be one of {sorted(self.ALGOS)}, not {algo!r}")
         self.ctx = ctx
+        self.algo = algo
+        self.h = None
         h = C.c_void_p()
-        check(lib().psf_kvmap_create(ctx.h, capacity, lr_type, alpha, beta, lambda1, lambda2, C.byref(h)))
+        check(lib().psf_kvmap_create_algo(ctx.h, capacity, self.ALGOS[algo], lr_type, alpha, beta, lambda1,
+                                          lambda2, C.byref(h)))
         self.h = h
         self._keepalive = []
 
@@ -255,6 +262,27 @@ class KVMap:
         a, b, c, d = C.c_int64(), C.c_double(), C.c_double(), C.c_uint64()
         check(lib().psf_kvmap_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
+
+    def export(self):
+        """The model as KVMap::WriteToFile enumerates it (kv_map.h:113-117):
+        (keys, w) of every entry with w != 0, in no particular order -- keys
+        as an int64 view of the uint64 keys, w float32, both on the device."""
+        n = C.c_size_t()
+        check(lib().psf_kvmap_export(self.h, None, None, 0, C.byref(n)))  # size query
+        dev = torch.device("cuda", self.ctx.device)
+        keys = torch.empty(n.value, dtype=torch.int64, device=dev)
+        w = torch.empty(n.value, dtype=torch.float32, device=dev)
+        if n.value:
+            check(lib().psf_kvmap_export(self.h, C.c_void_p(keys.data_ptr()), C.c_void_p(w.data_ptr()),
+                                         n.value, C.byref(n)))
+        return keys[:n.value], w[:n.value]
+
+    def write_file(self, path, sorted=True) -> int:
+        """KVMap::WriteToFile (kv_map.h:99-117): one "key\\tw" line per non-zero
+        weight, by ascending key when `sorted`; returns the line count."""
+        n = C.c_size_t()
+        check(lib().psf_kvmap_write_file(self.h, str(path).encode(), int(bool(sorted)), C.byref(n)))
+        return n.value
 
 
 class HostContext(Context):

@@ -4,9 +4,10 @@
 Two consumers of a received push message [KEY_CACHING, FIXING_FLOAT nb=1]
 whose m keys are sorted unique uint64:
 
-  kvmap   the async-SGD server: KVMap<Key,float,FTRLEntry>::SetValue
-          (kv_map.h:80-91, async_sgd.h:137-151) into a table already holding
-          the keys (steady state: every key found)
+  kvmap   the async-SGD server: KVMap<Key,float,Entry>::SetValue
+          (kv_map.h:80-91; --algo ftrl: FTRLEntry, async_sgd.h:137-151,
+          --algo adagrad: AdaGradEntry, async_sgd.h:159-171) into a table
+          already holding the keys (steady state: every key found)
   match   the BCD server: KVVector::SetValue's ParallelOrderedMatch PLUS
           (kv_vector.h:182-183) of the message into a sorted key/value store
           of D keys
@@ -16,7 +17,9 @@ each timed two ways, with HIP events on the context stream:
   fused   the decode is deferred and the consumer dequantises in-register
 
 plus the C restatement (oracle/psf_port.c) of the same consumer on one host
-core for scale.  Prints one JSON line.
+core for scale (FTRL only).  --export also times one model export
+(KVMap::WriteToFile's enumeration, kv_map.h:113-117) of the table after the
+pushes.  Prints one JSON line.
 """
 import argparse
 import ctypes as C
@@ -37,6 +40,10 @@ def main():
     ap.add_argument("--m", type=int, default=10_000_000, help="keys per push message")
     ap.add_argument("--dst", type=int, default=100_000_000, help="keys in the KVVector store")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--algo", choices=["ftrl", "adagrad"], default="ftrl", help="the KVMap's entry type")
+    ap.add_argument("--lambda1", type=float, default=10.0,
+                    help="the KVMap's L1 penalty (10 zeroes nearly every weight; 0.01 keeps most)")
+    ap.add_argument("--export", action="store_true", help="time one export of the table after the pushes")
     a = ap.parse_args()
     from parameter_server_amd import FIXING_FLOAT, KEY_CACHING
     from parameter_server_amd import filter as F
@@ -62,7 +69,7 @@ def main():
     payload = 12 * a.m  # 8 key + 4 value bytes per key
     ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
     res = {"what": "server-side consumer of a [KEY_CACHING, FIXING_FLOAT nb=1] push", "m": a.m,
-           "dst_keys": a.dst, "iters": a.iters}
+           "dst_keys": a.dst, "iters": a.iters, "algo": a.algo, "lambda1": a.lambda1}
 
     def timed(fn):
         fn()
@@ -75,8 +82,9 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.iters  # ms
 
-    # -- KVMap FTRL -------------------------------------------------------------
-    kv = F.KVMap(ctx, capacity=a.m, lr_type=2, alpha=0.01, beta=10.0, lambda1=10.0, lambda2=1.0)
+    # -- KVMap (FTRL / AdaGrad) -------------------------------------------------
+    kvconf = dict(lr_type=2, alpha=0.01, beta=10.0, lambda1=a.lambda1, lambda2=1.0, algo=a.algo)
+    kv = F.KVMap(ctx, capacity=a.m, **kvconf)
     w0 = m.clone()
     plain.decode(w0)
     kv.set_value(w0)  # insert every key once (steady state afterwards)
@@ -95,6 +103,34 @@ def main():
     res["kvmap"] = {"unfused_ms": round(t_u, 3), "fused_ms": round(t_f, 3),
                     "fused_GiBps_payload": round(payload / (t_f * 1e-3) / 2**30, 1),
                     "unfused_GiBps_payload": round(payload / (t_u * 1e-3) / 2**30, 1)}
+    if a.export:
+        # one export into arrays sized by stats()'s size, timed by the launch
+        # profiler (the kernel alone) and by the host clock (the whole call)
+        size = kv.stats()[3]
+        ok = torch.empty(size, dtype=torch.int64, device=dev)
+        ow = torch.empty(size, dtype=torch.float32, device=dev)
+        n = C.c_size_t()
+        from parameter_server_amd._lib import check, lib
+
+        def export():
+            check(lib().psf_kvmap_export(kv.h, C.c_void_p(ok.data_ptr()), C.c_void_p(ow.data_ptr()), size,
+                                         C.byref(n)))
+
+        export()  # warm-up
+        ctx.profile(True, kernels=["kvmap_export"])
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        export()
+        t_call = time.perf_counter() - t0
+        launches, ms, alg = ctx.profile_read()["kvmap_export"]
+        ctx.profile(False)
+        ctx.profile_reset()
+        res["export"] = {"slots": int((alg - 12 * n.value) / 32), "stored_keys": size, "nonzero": n.value,
+                         "kernel_us": round(ms * 1e3, 1), "alg_bytes": int(alg),
+                         "alg_GBps": round(alg / (ms * 1e-3) / 1e9, 1),
+                         "frac_of_6.29TBps": round(alg / (ms * 1e-3) / 6.29e12, 3),
+                         "call_us": round(t_call * 1e6, 1)}
+        del ok, ow
     del kv
 
     # -- KVVector ordered match (PLUS) ------------------------------------------
@@ -118,7 +154,7 @@ def main():
     # per-kernel HIP-event breakdown of the fused paths
     ctx.profile(True)
     ctx.profile_reset()
-    kv2 = F.KVMap(ctx, capacity=a.m, lr_type=2, alpha=0.01, beta=10.0, lambda1=10.0, lambda2=1.0)
+    kv2 = F.KVMap(ctx, capacity=a.m, **kvconf)
     for _ in range(3):
         mt_fused()
         w = m.clone()
