@@ -1,6 +1,6 @@
 // FIXING_FLOAT's dequantise (fixing_float.h:89-101), shared by the decode
 // kernels (ff_kernels.h) and the uncompress kernels that decode FIXING_FLOAT
-// codes as they leave a COMPRESSING stream (snappy.hip).  The two must give the
+// codes as they leave a COMPRESSING stream (snappy_uncompress.h).  The two must give the
 // same bits, so there is one definition.
 #pragma once
 #include <hip/hip_runtime.h>

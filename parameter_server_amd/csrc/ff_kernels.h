@@ -509,7 +509,7 @@ __device__ __forceinline__ void store_codes(uint8_t* __restrict__ out, size_t g,
 // FfJob::flags bit 2: the job's codes go to the layout of psf_internal.h's
 // StoredLayout -- fragment k's 64 KiB at hdr + 65539 k + 3, its literal tag
 // before it, the varint header first -- so COMPRESSING leaves a stream whose
-// fragments all come out stored where it is (snappy.hip K-place).  A group's
+// fragments all come out stored where it is (snappy_compress.h K-place).  A group's
 // code dword(s) land misaligned by (hdr + 3k + 3) mod 4: one unaligned
 // global store (gfx950 runs in unaligned mode: as fast as the aligned stream,
 // tools/ustore_probe.hip); the tags and the header are constants, written by

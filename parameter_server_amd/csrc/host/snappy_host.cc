@@ -265,7 +265,7 @@ void SnappyBatch::finish() {
     j.out.bytes = h.size;
     if (j.compress && h.pad == kStoredInPlace) {
       // every fragment came out stored: the stream FIXING_FLOAT wrote is the
-      // result (snappy.hip K-place), the compressor's buffer goes unused
+      // result (snappy_compress.h K-place), the compressor's buffer goes unused
       Buffer o = j.in;
       o.bytes = h.size;
       o.layout = kLayoutPlain;

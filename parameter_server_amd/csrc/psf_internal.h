@@ -256,7 +256,7 @@ constexpr uint32_t kSnappyFragOut = 76544;  // >= MaxCompressedLength(64 KiB), 2
 // start at hdr + 65539 k + 3; the last fragment has its own tag.  FIXING_FLOAT
 // writes its codes straight into this layout when COMPRESSING follows
 // (Buffer::kLayoutStored), and COMPRESSING leaves a stream whose fragments all
-// come out stored where it is (snappy.hip K-place).
+// come out stored where it is (snappy_compress.h K-place).
 constexpr uint32_t kStoredFragBytes = 65536 + 3;
 __host__ __device__ __forceinline__ uint32_t snappy_varint_len(uint64_t v) {
   uint32_t n = 1;
@@ -316,7 +316,7 @@ constexpr SkipCum make_skip() {
 }
 // bytes allocated after a stored stream: the compressor's aligned reads past a
 // fragment's end (64), and the room an in-place compressed stream may grow
-// into (snappy.hip kShiftMax)
+// into (snappy_compress.h kShiftMax)
 constexpr uint32_t kStoredSlack = 192;
 __host__ __device__ __forceinline__ uint64_t stored_alloc_bytes(const StoredLayout& s) {
   return stored_stream_bytes(s) + kStoredSlack;

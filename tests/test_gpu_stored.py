@@ -208,7 +208,7 @@ def test_compress_stored_in_place(ctx, port, case):
     shorter (down by whole fragments), byte-identical to 1.1.8.  Streams that
     grow by at most 64 bytes (and never shrink below a fragment's stored
     start) are rewritten in place by K-place, the later fragments moved right
-    (snappy.hip kPlaceShift; "grow_early": shifts up to 55 bytes, then
+    (snappy_compress.h kPlaceShift; "grow_early": shifts up to 55 bytes, then
     fragments whose final literal starts 25 bytes in, so the stash of each
     fragment's first bytes supplies what the left neighbour may have
     overwritten inside a final literal; "grow_short_tail*": a last
